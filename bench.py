@@ -19,10 +19,16 @@ every group's crops come from its own generator, so the global batch does not de
 32 groups per rank (weak scaling, no data-path collective), `dist.get_world_size() == N` is
 asserted, time = max over ranks, value = all ranks' frames / that time.
 
-Also reported, on the same JSON line (rank 0):
+A plain run sets up, autotunes the conv tiles, warms up, times the --steps steps and prints one
+JSON line (rank 0) with the headline figure and what the timed steps themselves yield:
   roofline       -- the network (fused stem + implicit-GEMM MFMA conv stack + fused
                     deconv/head): 14.47 GFLOP/frame x 128 frames per replay / its
-                    HIP-event time on the launch stream, against the dense bf16 peak;
+                    HIP-event time on the launch stream, against the dense bf16 peak.
+`--dump-outputs DIR` writes what the last timed step computed (heatmaps, joints, epipolar loss,
+triangulated joints) as DIR/<name>.npy; the inputs are seeded, so two builds compare output for
+output.
+
+`--full` adds every other leg and check, on the same JSON line:
   mpjpe_vs_ref_mm -- the bench chain's triangulated joints against the CPU oracle chain
                     (fp32 reference network + soft-argmax + affine + fp64 triangulation)
                     on the same first input batch, as run/test/test_triangulate.py:98-102
@@ -73,6 +79,13 @@ def parse():
                     help='infer: BASELINE metric (fwd + triangulate); train: configs[3] training step')
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--full', action='store_true',
+                    help='infer mode: after the headline leg also run the other legs and checks (training step, fp32 / '
+                         'fp16x3 / configs[1] / configs[4] / control legs, the oracle comparisons, the peaked-heatmap '
+                         'parity, the CPU baseline); the per-leg options below apply to such a run')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most '
+                         '64 MB; rank 0)')
     ap.add_argument('--groups', type=int, default=32, help='4-view groups per GPU per step')
     ap.add_argument('--batches', type=int, default=3, help='distinct input batches rotated over the timed steps')
     ap.add_argument('--layers', type=int, default=50)
@@ -496,7 +509,7 @@ def rank_meta(args, rank, world, dev):
     return shard, meta, host
 
 
-def time_pipeline(args, precision, dev, rank, steps, warmup, nbatch, autotune, dist=None, world=1):
+def time_pipeline(args, precision, dev, rank, steps, warmup, nbatch, autotune, dist=None, world=1, keep_last=False):
     """Build, (auto)tune, capture and time the pipeline in one precision; returns a dict."""
     net = build_model(args.layers, args.size, precision, dev)
     shard, meta, host = rank_meta(args, rank, world, dev)
@@ -570,6 +583,11 @@ def time_pipeline(args, precision, dev, rank, steps, warmup, nbatch, autotune, d
         elapsed = time.perf_counter() - t0
         net_ms = float(np.mean([a.elapsed_time(b) for a, b, _, _ in ev]))
         geo_ms = float(np.mean([d.elapsed_time(c) for _, _, c, d in ev]))
+        last = None
+        if keep_last:   # what the last timed step returned (--dump-outputs)
+            r = reps[(steps - 1) % nbatch]
+            last = {'heatmaps': r.hm, 'joints_2d': r.out[0], 'epipolar_loss': r.out[1], 'joints_3d': r.out[2]}
+            last = {k: v.detach().cpu().numpy().copy() for k, v in last.items()}
         # the first batch's outputs, for the MPJPE check
         r = reps[0]
         coords, loss, X = r.run_geo(r.run_net())
@@ -577,7 +595,27 @@ def time_pipeline(args, precision, dev, rank, steps, warmup, nbatch, autotune, d
     return {'elapsed': elapsed, 'net_ms': net_ms, 'geo_ms': geo_ms, 'X0': X.detach().cpu().numpy().copy(),
             'coords0': coords.detach().cpu().numpy().copy(), 'hm0': r.hm.detach().cpu().clone(),
             'use_graph': use_graph, 'tuned': tuned, 'loss0': float(loss), 'meta': r.meta, 'host': host,
-            'shard': shard, 'chunks': args.chunks if args.chunks is not None else plan.default_chunks()}
+            'shard': shard, 'chunks': args.chunks if args.chunks is not None else plan.default_chunks(),
+            'last': last}
+
+
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> numpy array) as path/<name>.npy, float64 kept, everything
+    else as float32, DUMP_BYTES of data at most in all (smallest first; an array over an even share of
+    what is left is cut to a fixed seeded sample of its elements, flattened, in index order)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: (a if a.dtype == np.float64 else a.astype(np.float32)) for k, a in arrays.items()}
+    left = DUMP_BYTES - 1024 * len(arrays)   # room for the .npy headers
+    for n, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].nbytes)):
+        share = left // (len(arrays) - n)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def triangulation_parity_all_ranks(res, dev):
@@ -733,9 +771,15 @@ def infer_main(args):
     torch.cuda.set_device(dev)
     rank, local, world, dist = init_ranks(args, backend, device=dev)
     frames = 4 * args.groups
+    if not args.full:   # a plain run: the headline leg alone, every other leg and check off
+        args.train_steps = args.fp32_steps = args.parity_steps = args.c1_steps = args.c4_steps = 0
+        args.control_steps = args.peaked_steps = 0
+        args.no_cpu_baseline = args.no_mpjpe = True
     res = time_pipeline(args, args.precision, dev, rank, args.steps, args.warmup, args.batches,
-                        not args.no_autotune, dist, world)
-    tri_all = triangulation_parity_all_ranks(res, dev)
+                        not args.no_autotune, dist, world, keep_last=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res['last'])
+    tri_all = triangulation_parity_all_ranks(res, dev) if args.full else None
     elapsed = pdist.max_over_ranks(res['elapsed'], device=dev)
     value = pdist.throughput(frames, args.steps, world, elapsed)
     per_rank = gather_per_rank([frames * args.steps, res['elapsed']], dist, device=dev)
@@ -1061,6 +1105,8 @@ def train_main(args):
     rank, local, world, dist = init_ranks(args, backend, device=dev)
     line = run_training(args, dev, rank, world, dist, args.steps, args.warmup)
     if rank == 0:
+        if args.dump_outputs:   # the step returns its loss
+            dump_outputs(args.dump_outputs, {'loss': np.array(line['loss'], np.float64)})
         print(json.dumps(line, default=_json_default))
     if dist is not None:
         dist.destroy_process_group()

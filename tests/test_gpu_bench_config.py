@@ -21,6 +21,8 @@ measured bands, and within 4x the reference fp32 path's own deviation from fp64.
 (benchmarked mode) -- bands from the measured deviation: soft-argmax at
 beta = 100 on the peakless heatmaps of a random-weight network turns bf16's ~0.02 heatmap
 deviation into joint moves of tens of pixels."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -232,3 +234,51 @@ def test_configs1_batch64_plan_end_to_end(cuda, monkeypatch):
     err = (hm2.cpu() - ref).abs()
     print('configs1 batch-64 plan: rows 0-1 vs the oracle, heatmaps max %.3g mean %.3g' % (err.max(), err.mean()))
     assert float(err.max()) < BANDS['bf16']['hm_max'] and float(err.mean()) < BANDS['bf16']['hm_mean']
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_steps_outputs(cuda, monkeypatch, capsys, tmp_path):
+    """`bench.py --gpus 1 --steps 5 --warmup 1 --dump-outputs DIR` (R18@128, 2 groups, fp32, heuristic
+    tiles): a plain run reports the headline leg alone (ms_per_step consistent with value; every leg that
+    --full adds absent), and DIR holds what the last timed step (step 4 = input batch 4 % 3 = 1) computed:
+    the heatmaps bit-identical to an eager run of the same plan on that batch (not batch 0's: the maps of
+    two batches differ by far more than the 1e-3 parity bar), the joints, loss and triangulated joints
+    those heatmaps give (1e-2 px; loss 1e-5 relative, the fp32 band above; BASELINE's 1e-2 mm for the
+    DLT against the oracle's triangulation of the same joints)."""
+    import json
+    from oracle import geometry_ref as G
+    layers, size, groups, steps = 18, 128, 2, 5
+    out = tmp_path / 'dump'
+    monkeypatch.setattr('sys.argv', ['bench.py', '--gpus', '1', '--steps', str(steps), '--warmup', '1', '--layers',
+                                     str(layers), '--size', str(size), '--groups', str(groups), '--precision', 'fp32',
+                                     '--no-autotune', '--dump-outputs', str(out)])
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert line['metric'] == bench.METRIC and line['unit'] == 'frames/s' and line['higher_is_better'] is True
+    assert line['steps'] == steps and line['warmup'] == 1 and line['dtype'] == 'fp32' and line['ms_per_step'] > 0
+    assert abs(line['value'] * line['ms_per_step'] * 1e-3 / (4 * groups) - 1) < 1e-3   # frames/s x s/step = frames
+    for leg in ('train_mode', 'fp32_mode', 'parity_mode', 'configs1', 'configs4', 'control', 'cpu_baseline',
+                'mpjpe_vs_ref_mm', 'peaked_parity', 'random_weight_chain_vs_ref', 'triangulation_same_2d_mm_all_ranks'):
+        assert line[leg] is None, leg
+    got = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+    assert {k: (v.shape, v.dtype) for k, v in got.items()} == {
+        'heatmaps': ((4 * groups, 16, size // 4, size // 4), np.float32), 'joints_2d': ((4, groups, 16, 2), np.float32),
+        'epipolar_loss': ((), np.float32), 'joints_3d': ((groups, 16, 3), np.float64)}
+    net = bench.build_model(layers, size, 'fp32', cuda)
+    meta, host = synthetic_meta(groups, cuda, image_size=size)
+    plan = net.plan(cuda)
+    with torch.no_grad():
+        hm = {}
+        for b in (0, (steps - 1) % 3):
+            rep = bench.Replayer(plan, bench.input_views(list(range(groups)), size, b, cuda), meta, groups, None,
+                                 False, cuda)
+            hm[b] = rep.stage_net().clone()
+        coords, loss, X = rep.stage_geo(torch.from_numpy(got['heatmaps']).to(cuda))
+        torch.cuda.synchronize()
+    assert float((hm[1] - hm[0]).abs().max()) > 1e-2
+    assert np.array_equal(got['heatmaps'], hm[1].cpu().numpy())
+    jerr = float(np.abs(got['joints_2d'] - coords.cpu().numpy()).max())
+    lerr = abs(float(got['epipolar_loss']) / float(loss) - 1)
+    p2d = got['joints_2d'].transpose(1, 0, 2, 3).reshape(groups * 4, 16, 2).astype(np.float64)
+    xerr = float(np.abs(got['joints_3d'] - G.triangulate_poses(host['cams'], p2d)).max())
+    print('plain run dump vs recomputation: joints %.3g px, loss rel %.3g, triangulation %.3g mm' % (jerr, lerr, xerr))
+    assert jerr < 1e-2 and lerr < 1e-5 and xerr < 1e-2

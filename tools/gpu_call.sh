@@ -9,7 +9,8 @@
 #   tests:ARGS          pytest -m gpu over ARGS (files, -k expressions), e.g. tests:tests/test_gpu_split.py,-k,tail
 #   suite               the whole GPU test suite
 #   smoke               __graft_entry__.smoke()
-#   bench[@NAME]:ARGS   python bench.py ARGS -> OUTDIR/NAME.json (default name bench)
+#   bench[@NAME]:ARGS   python bench.py ARGS -> OUTDIR/NAME.json (default name bench); ARGS --full: every leg
+#                       (parity_mode, train_mode, ...) on the line, not the headline leg alone
 #   replay@NAME:ARGS    tuned bench forward under rocprofv3 --kernel-trace -> OUTDIR/NAME_replay_breakdown.txt
 #                       (ARGS: extra bench args, e.g. --precision,fp16x3)
 #   pmc@NAME:ARGS       HBM traffic per forward launch (FETCH_SIZE, WRITE_SIZE passes) -> OUTDIR/NAME_pmc_traffic.txt
@@ -21,6 +22,7 @@ OUT=${1:?usage: gpu_call.sh OUTDIR STEP...}
 shift
 mkdir -p "$OUT"
 export TMPDIR=/tmp
+# every leg of a --full run off: with ARGS = --full and one leg's option (--parity-steps 10), that leg alone
 LEAN="--no-cpu-baseline --no-mpjpe --fp32-steps 0 --parity-steps 0 --train-steps 0 --c1-steps 0 --peaked-steps 0 --c4-steps 0 --control-steps 0"
 
 fail() { echo "step '$1' failed (exit $2)"; exit "$2"; }
