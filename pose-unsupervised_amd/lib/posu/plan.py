@@ -14,6 +14,8 @@ plus the ordered list of kernel launches of one forward pass
 All launches go to PyTorch's current stream, so a forward can be captured in a
 torch.cuda.CUDAGraph (hipGraph) by the caller.
 """
+from collections import namedtuple
+
 import torch
 
 from . import ops
@@ -92,10 +94,10 @@ TILES_128X8 = True
 # measured 1 % faster with it (2.237 / 2.250 vs 2.267 / 2.270 ms; 1.331 / 1.327 vs 1.345 / 1.342 ms,
 # profiles/r06/ksplit_bf16_ab_r6ah.txt; round 5's plan showed no gain), and the line's `control` leg times
 # the plan without it.  Where the tuner picks it, the 2-byte plans' last bits depend on the tuned table
-# (reproducible under a fixed --tune-file); the parity mode keeps it out (TILES_KSPLIT_F16X3): every
-# candidate tile of the split dtype sums alike, so its results do not depend on the tuning
+# (reproducible under a fixed --tune-file).  The split dtype never gets tile 39: every candidate tile of
+# the parity mode sums alike, so its results do not depend on the tuning (and the A/B was at noise level:
+# 5.689 / 5.603 vs 5.675 / 5.704 ms, profiles/r06/ksplit_bf16_ab_r6ah.txt)
 TILES_KSPLIT = True
-TILES_KSPLIT_F16X3 = False
 # the split dtype's staggered eight-wave tiles (31, 47 / 55; round 6) among its autotuner candidates
 TILES_SPLIT_SG = True
 
@@ -106,9 +108,6 @@ _TUNE_TIMES = {}   # geometry key -> {tile: best ms of the reps}, the last tunin
 _REFINE_TIMES = {}  # geometry key -> {tile: ms per whole forward}, the in-context stage's measurements
 # the in-context second tuning stage (PoseResNetPlan._refine_in_context)
 REFINE_IN_CONTEXT = True
-# its candidates: the per-launch times within REFINE_WITHIN of a geometry's best, at most REFINE_TOP of them
-REFINE_WITHIN = 0.25
-REFINE_TOP = 3
 
 
 class _Tuner:
@@ -135,17 +134,16 @@ def _tile_candidates(cout, code=None, ksplit=False):
     # 23 / 31: the eight-wave tiles with waves 4-7 staggered by half a K-tile; 7 / 15: 128x128 with
     # eight staggered waves (2x4 / 4x2 wave grids)
     sg = [23 + 8 * (t == 6) for t in c if t in (5, 6)] + ([7, 15] if cpad % 128 == 0 and TILES_128X8 else [])
-    # (tile 32, the persistent 256x64 four-wave instance, is left out: it spills 928 B per lane to
-    # scratch and took ~1.2 ms per launch in the tuning trials, 10x the other tiles)
+    rings = c + [t + 8 for t in c if t <= 4] + [t + 16 for t in c if t != 5]
     if code == ops.F16X3:   # the split dtype: plain rings (no persistent stream), the unstaggered (7 / 15)
-        # and (round 6) staggered (47 / 55) eight-wave 128x128 tiles, the staggered 256x128 tile (31) and the
-        # two-K-group tile (39)
-        return c + [t + 8 for t in c if t <= 4] + [t + 16 for t in c if t != 5] + (
-            [7, 15] + ([47, 55, 31] if TILES_SPLIT_SG else []) + ([39] if ksplit and TILES_KSPLIT_F16X3 else [])
-            if cpad % 128 == 0 else [])
+        # and (round 6) staggered (47 / 55) eight-wave 128x128 tiles and the staggered 256x128 tile (31); never
+        # the two-K-group tile (39, TILES_KSPLIT above)
+        return rings + ([7, 15] + ([47, 55, 31] if TILES_SPLIT_SG else []) if cpad % 128 == 0 else [])
     if ksplit and code in (ops.BF16, ops.F16) and cpad % 128 == 0:
         sg = sg + [39]
-    return c + [t + 8 for t in c if t <= 4] + [t + 16 for t in c if t != 5] + [t + 32 for t in c if t != 0] + sg
+    # (tile 32, the persistent 256x64 four-wave instance, is left out: it spills 928 B per lane to
+    # scratch and took ~1.2 ms per launch in the tuning trials, 10x the other tiles)
+    return rings + [t + 32 for t in c if t != 0] + sg
 
 
 def _tuned(key, cout, launch):
@@ -269,13 +267,12 @@ CHAINED_TAILS = True
 # under CHAINED_TAILS too)
 S2_CHAIN = True
 # the identity Bottlenecks at 384x384 (R152, BASELINE configs[4]) as conv1 + the streamed tail
-# (round 5): layer3 at W = 24 (not chained), layer2 at W = 48 (chained)
+# (round 5): layer3 at W = 24 (not chained), layer2 at W = 48 (chained).  Chaining layer3's W = 24 tails
+# like the 256x256 ones (2-row tiles, three m-tiles per wave, round 6) measured even with each conv1 a
+# launch of its own after the plain 6-row tail (configs[4] 9.82 / 10.01 vs 9.97 / 9.97 k frames/s,
+# profiles/r06/w24_chain_ab_r6l.txt) -- the 2-row tiles' weight stream (a third of the MFMAs per fragment)
+# costs what the conv1 launches cost -- so the plan has no such variant
 TAIL_W24 = True
-# layer3 at W = 24: the identity tails chained like the 256x256 ones (2-row tiles, three m-tiles per wave,
-# round 6).  Off: measured even with each conv1 a launch of its own after the plain 6-row tail (configs[4]
-# 9.82 / 10.01 vs 9.97 / 9.97 k frames/s, profiles/r06/w24_chain_ab_r6l.txt) -- the 2-row tiles' weight
-# stream (a third of the MFMAs per fragment) costs what the conv1 launches cost
-TAIL_W24_CHAIN = False
 # the split dtype's identity Bottlenecks of layer1 / layer2 / layer3 as conv1 + the streamed tail
 # (chained), layer1's first block as conv1 + the down tail (chained), round 6; False: the conv launches
 SPLIT_TAILS = True
@@ -296,13 +293,10 @@ CHAIN_LAYERS_2B = False
 # chained (layer1 -> layer2 inside a half, layer2 -> layer3 through a whole-batch buffer) -- 5.47-5.64
 # vs 5.60-5.75 ms per forward at 32 x 4 (profiles/r06/chunks_ab_r6vwx.txt; 4 chunks slower: the halved
 # grids cost more).  The bf16 headline measured slower chunked (2.376 / 2.378 vs 2.325 / 2.346 ms) and
-# keeps 1.
+# keeps 1.  Both ends are sliced, the late stage like the early one: a late stage in quarters or eighths
+# measured no better than in halves (5.619 / 5.784, 5.727 / 5.714 vs 5.639 / 5.661 ms, same file).
 CHUNKS_F16X3 = 2
-# which ends of the network a chunked run slices (A/B switches; both by default)
-CHUNK_EARLY = True   # stem..layer2 (EARLY_LAYERS = 1: stem..layer1)
-EARLY_LAYERS = 2     # layers in the chunked early stage (1 .. 3)
-CHUNK_LATE = True    # deconv2..head
-LATE_CHUNKS = 0      # > 0: the late stage's own slice count (0: the run's chunks)
+EARLY_LAYERS = 2     # layers in the chunked early stage (1 .. 3): stem..layer2 (1: stem..layer1)
 _FUSED_MAX_BYTES = (1 << 31) - 256   # the fused kernels address x / y with 32-bit byte offsets
 
 
@@ -314,234 +308,241 @@ def _fused_fits(x, cout):
     return px * max(x.shape[3], cout) * es < _FUSED_MAX_BYTES
 
 
+_2B = (ops.BF16, ops.F16)
+_SPLIT = (ops.F16X3,)
+# Where a fused kernel runs: the dtypes, the map width, the multiple its rows must be of (its row tile), the
+# chained entry points it has there ('next': + the next block's conv1, 'layer': + the next layer's first
+# conv1), and its switches -- built: read when a plan is constructed (off: the packs are not made), live:
+# read at every call.
+_At = namedtuple('_At', 'codes width rows chains built live', defaults=((), None, None))
+# What a fused kernel is built for: the (Cout, K) pack shapes of conv1, conv2 and conv3, or of the
+# conv3 | downsample dual pack, in logical k (a pack row holds cmul(code) stored halves per k), conv2's
+# stride, and where it runs.
+_Kernel = namedtuple('_Kernel', 'conv1 conv2 conv3 dual stride at')
+_GEOMETRY = {
+    # layer1 at 64-wide maps, one launch per block: the identity blocks, the first block with its downsample
+    'fused': _Kernel((64, 256), (64, 576), (256, 64), None, 1, (_At(_2B, 64, 1),)),
+    'fused_down': _Kernel((64, 64), (64, 576), None, (256, 128), 1, (_At(_2B, 64, 1),)),
+    # conv1 (a conv launch), then conv2 + the dual GEMM in one: layer1's first block (2-row tiles) and
+    # layer2's, strided
+    'down_tail': _Kernel((64, 64), (64, 576), None, (256, 128), 1,
+                         (_At(_SPLIT, 64, 2, ('next',), 'SPLIT_TAILS', 'SPLIT_TAILS'),
+                          _At(_2B, 96, 2, ('next',), 'TAIL_W96', 'TAIL_W96'))),
+    's2_tail': _Kernel((128, 256), (128, 1152), None, (512, 384), 2, (_At(_2B, 64, 8, ('next',), live='S2_TAIL'),)),
+    # conv1, then the register-streamed conv2 + conv3 + residual tail: the identity blocks of layers 1-3
+    # (the split dtype at 256x256 only; 2-byte layer1 at 64-wide maps runs 'fused'; W = 48 / 24: R152 at
+    # 384x384, BASELINE configs[4])
+    'l1': _Kernel((64, 256), (64, 576), (256, 64), None, 1,
+                  (_At(_SPLIT, 64, 2, ('next', 'layer'), 'SPLIT_TAILS'), _At(_2B, 96, 2, ('next',), 'TAIL_W96'))),
+    'l2': _Kernel((128, 512), (128, 1152), (512, 128), None, 1,
+                  (_At(_2B, 32, 4, ('next', 'layer')), _At(_SPLIT, 32, 4, ('next', 'layer'), 'SPLIT_TAILS'),
+                   _At(_2B, 48, 2, ('next',), live='TAIL_W24'))),
+    'l3': _Kernel((256, 1024), (256, 2304), (1024, 256), None, 1,
+                  (_At(_2B, 16, 8, ('next', 'layer')), _At(_SPLIT, 16, 8, ('next', 'layer'), 'SPLIT_TAILS'),
+                   _At(_2B, 24, 6, (), live='TAIL_W24'))),
+}
+
+
+def _on(switch):
+    return switch is None or bool(globals()[switch])
+
+
 class _Block:
-    __slots__ = ('convs', 'down', 'dual', 'w1f', 'w3f', 'w3d', 'l1', 'l2', 'l3', 'wst', 'chain', 'wsn', 'ws2', 'ws2n',
-                 'wsd', 'wsdn', 'dscale', 'code', 'xchain', 'wsx')
+    """One residual block: its packs and the launches it makes.  select() names the variant
+    that runs on an input, run() executes it:
+
+        'fused' / 'fused_down'   posu_bottleneck_fwd / posu_bottleneck_down_fwd
+        'down_tail'              conv1, posu_bottleneck_down_tail_stream_fwd (chained: with s1n / b1n)
+        's2_tail'                conv1, posu_bottleneck_s2_tail_fwd (chained: .._s2_tail_next_fwd)
+        'tail'                   conv1 (unless handed in), posu_bottleneck_tail_stream_fwd (chained 'next':
+                                 .._stream_next_fwd, 'layer': .._stream_chain_fwd)
+        'dual'                   conv1 (unless handed in), conv2, the conv3 | downsample dual GEMM
+        'convs'                  the plain conv launches, the residual in the last one's epilogue
+    """
+    __slots__ = ('convs', 'down', 'dual', 'code', 'kind', 'packs', 'chain', 'xchain', 'dscale')
 
     def __init__(self, blk, code, bk):
         names = ['conv1', 'conv2', 'conv3'] if hasattr(blk, 'conv3') else ['conv1', 'conv2']
         self.convs = []
         self.down = None
         self.dual = None
-        self.w1f = self.w3f = None   # conv1 / conv3 packed for the fused kernel (permuted K)
-        self.w3d = None              # the fused first block's [w3*s3 | wd*sd] (permuted conv3 K)
-        self.l1 = False              # a layer1 identity block on the streamed tail (the split dtype, round 6)
-        self.l2 = False              # a layer2 identity block (fused kernel, the convs' own packs)
-        self.l3 = False              # a layer3 identity block (conv1, then the fused conv2 + conv3 tail)
-        self.wst = None              # layer2 / layer3: the tail's per-wave weight streams (pack_tail_stream)
-        self.chain = None            # the next identity block's conv1 (_Conv) when the tails chain
-        self.wsn = None              # the streams with that conv1 appended (pack_tail_stream(.., w1n))
-        self.ws2 = None              # layer2 block 0: the strided tail's weight streams (pack_s2_tail_stream)
-        self.ws2n = None             # ... with the next block's conv1 appended (the chained strided tail)
-        self.wsd = None              # split layer1 block 0: the down tail's streams (pack_down_tail_stream)
-        self.wsdn = None             # ... with the next block's conv1 appended
-        self.dscale = None           # ... the dual GEMM's epilogue scale (2^-e)
         self.code = code
-        self.xchain = None           # split: the next layer's first conv1 (_Conv), chained by this last tail
-        self.wsx = None              # ... its tail stream (pack_tail_stream(.., that conv1): NX = 2)
+        self.kind = None     # 'l1' / 'l2' / 'l3': the identity block of that layer the streamed tail is built for
+        # the fused kernels' packs by variant: 'fused' (conv1, conv3 with permuted K), 'fused_down' ([w3*s3 |
+        # wd*sd], permuted conv3 K), 'tail' / 'down_tail' / 's2_tail' (the per-wave weight streams) and
+        # '.._next' / 'tail_layer' (the streams with the chained conv1 appended)
+        self.packs = {}
+        self.chain = None    # the next block's conv1 (_Conv) where this block's tail can chain it
+        self.xchain = None   # the next layer's first conv1 (_Conv), chained by this layer's last tail
+        self.dscale = None   # the down tail's dual-GEMM epilogue scale (2^-e; ones in 2-byte plans)
         ds = blk.downsample
         if ds is not None and len(names) == 3 and ds[0].kernel_size == (1, 1) and \
                 blk.conv3.weight.shape[1] % bk == 0 and ds[0].weight.shape[1] % bk == 0:
             for nm in names[:2]:
                 self.convs.append(_Conv(getattr(blk, nm), getattr(blk, 'bn' + nm[-1]), True, code, bk))
             self.dual = _DualTail(blk.conv3, blk.bn3, ds[0], ds[1], code)
-            c1, c2 = self.convs
-            if code in (ops.BF16, ops.F16) and self.dual.stride2 == 1 and self.dual.cout == 256 and \
-                    c1.k == 1 and c1.stride == 1 and c1.w.shape == (64, 64) and \
-                    c2.k == 3 and c2.stride == 1 and c2.pad == 1 and c2.w.shape == (64, 576) and \
-                    self.dual.w.shape[1] >= 128:
-                self.w3d = pack_bottleneck_down_weight(self.dual.w, 64)
-            if code == ops.F16X3 and SPLIT_TAILS and self.dual.stride2 == 1 and self.dual.cout == 256 and \
-                    c1.k == 1 and c1.stride == 1 and tuple(c1.w.shape) == (64, 128) and \
-                    c2.k == 3 and c2.stride == 1 and c2.pad == 1 and tuple(c2.w.shape) == (64, 1152) and \
-                    tuple(self.dual.w.shape) == (256, 256):
-                self.wsd = pack_down_tail_stream(c2.w, self.dual.w)
+            c2 = self.convs[1]
+            if self._built_for('fused_down'):
+                self.packs['fused_down'] = pack_bottleneck_down_weight(self.dual.w, 64)
+            if self._built_for('down_tail'):
+                self.packs['down_tail'] = pack_down_tail_stream(c2.w, self.dual.w)
                 self.dscale = (self.dual.scale if self.dual.scale is not None else
-                               torch.ones(256, device=self.dual.shift.device))
-            if code in (ops.BF16, ops.F16) and TAIL_W96 and self.dual.stride2 == 1 and self.dual.cout == 256 and \
-                    c1.k == 1 and c1.stride == 1 and tuple(c1.w.shape) == (64, 64) and \
-                    c2.k == 3 and c2.stride == 1 and c2.pad == 1 and tuple(c2.w.shape) == (64, 576) and \
-                    tuple(self.dual.w.shape) == (256, 128):
-                self.wsd = pack_down_tail_stream(c2.w, self.dual.w)
-                self.dscale = torch.ones(256, device=self.dual.shift.device)
-            if code in (ops.BF16, ops.F16) and self.dual.stride2 == 2 and self.dual.cout == 512 and \
-                    c1.k == 1 and c1.stride == 1 and c1.w.shape == (128, 256) and \
-                    c2.k == 3 and c2.stride == 2 and c2.pad == 1 and c2.w.shape == (128, 1152) and \
-                    tuple(self.dual.w.shape) == (512, 384):
-                self.ws2 = pack_s2_tail_stream(c2.w, self.dual.w)
+                               torch.ones(self.dual.cout, device=self.dual.shift.device))
+            if self._built_for('s2_tail'):
+                self.packs['s2_tail'] = pack_s2_tail_stream(c2.w, self.dual.w)
             return
         for nm in names:
             self.convs.append(_Conv(getattr(blk, nm), getattr(blk, 'bn' + nm[-1]), True, code, bk))
         if ds is not None:
             self.down = _Conv(ds[0], ds[1], False, code, bk)
-        elif code in (ops.BF16, ops.F16) and len(names) == 3 and self._fusable_shape():
-            self.w1f = pack_bottleneck_conv1_weight(blk.conv1.weight, ops.torch_dtype(code))
-            self.w3f = pack_bottleneck_conv3_weight(blk.conv3.weight, ops.torch_dtype(code))
-            # (the same blocks at 96-wide maps run conv1 + the streamed tail: 'l1' at W = 96)
-            self.l1 = TAIL_W96 and self._layer1_shape()
-            if self.l1:
-                self.wst = pack_tail_stream(self.convs[1].w, self.convs[2].w)
-        elif code in (ops.BF16, ops.F16, ops.F16X3) and len(names) == 3:
-            # (the split dtype: its packs hold 2 K halves per row; layer1 too -- the fused layer1 kernel
-            # does not hold pairs -- on the streamed tail, round 6)
-            cm = ops.cmul(code)
-            self.l1 = code == ops.F16X3 and SPLIT_TAILS and self._layer1_shape(cm)
-            self.l2 = (code != ops.F16X3 or SPLIT_TAILS) and self._layer2_shape(cm)
-            self.l3 = (code != ops.F16X3 or SPLIT_TAILS) and self._layer3_shape(cm)
-            if self.l1 or self.l2 or self.l3:
-                self.wst = pack_tail_stream(self.convs[1].w, self.convs[2].w)
+        if self._built_for('fused'):
+            self.packs['fused'] = (pack_bottleneck_conv1_weight(blk.conv1.weight, ops.torch_dtype(code)),
+                                   pack_bottleneck_conv3_weight(blk.conv3.weight, ops.torch_dtype(code)))
+        self.kind = next((k for k in ('l1', 'l2', 'l3') if self._built_for(k)), None)
+        if self.kind is not None:
+            self.packs['tail'] = pack_tail_stream(self.convs[1].w, self.convs[2].w)
+
+    def _built_for(self, kernel):
+        """This block's convolutions are the ones `kernel` is built for (_GEOMETRY), in a dtype it has,
+        that row's construction switch on."""
+        g = _GEOMETRY[kernel]
+        if self.down is not None or (self.dual is None) != (g.dual is None) or len(self.convs) != (2 if g.dual else 3):
+            return False
+        c1, c2 = self.convs[:2]
+        last, shape = (self.dual, g.dual) if g.dual else (self.convs[2], g.conv3)
+        cm = ops.cmul(self.code)
+        return (c1.k == 1 and c1.stride == 1 and c2.k == 3 and c2.stride == g.stride and c2.pad == 1 and
+                (last.stride2 == g.stride if g.dual else last.k == 1 and last.stride == 1) and
+                all(c.cout == co and tuple(c.w.shape) == (co, k * cm)
+                    for c, (co, k) in ((c1, g.conv1), (c2, g.conv2), (last, shape))) and
+                any(self.code in a.codes and _on(a.built) for a in g.at))
+
+    def _chains(self, how):
+        """The streamed tail of this block's kind has the `how`-chained entry point in this dtype."""
+        return self.kind is not None and any(self.code in a.codes and how in a.chains
+                                             for a in _GEOMETRY[self.kind].at)
 
     def link_next(self, nxt):
-        """Chain this identity block's streamed tail with the next block's conv1 (same layer, same
-        kind of tail)."""
-        if (self.l1 and nxt.l1) or (self.l2 and nxt.l2) or (self.l3 and nxt.l3):
+        """Chain this block's tail with the next block's conv1: identity tails of one kind, the down tail
+        and layer1's block 1, the strided tail and layer2's block 1."""
+        c2 = self.convs[1]
+        if self.kind is not None and self.kind == nxt.kind:
             self.chain = nxt.convs[0]
-            self.wsn = pack_tail_stream(self.convs[1].w, self.convs[2].w, self.chain.w)
-        elif self.wsd is not None and nxt.l1:   # split layer1: the down tail and block 1's conv1
+            self.packs['tail_next'] = pack_tail_stream(c2.w, self.convs[2].w, self.chain.w)
+        elif 'down_tail' in self.packs and nxt.kind == 'l1':
             self.chain = nxt.convs[0]
-            self.wsdn = pack_down_tail_stream(self.convs[1].w, self.dual.w, self.chain.w)
-        elif self.ws2 is not None and nxt.l2:   # layer2's strided tail and block 1's conv1
+            self.packs['down_tail_next'] = pack_down_tail_stream(c2.w, self.dual.w, self.chain.w)
+        elif 's2_tail' in self.packs and nxt.kind == 'l2':
             self.chain = nxt.convs[0]
-            self.ws2n = pack_s2_tail_stream(self.convs[1].w, self.dual.w, self.chain.w)
-
-    def _tail_kind(self, x):
-        """'l2' / 'l3' when this block runs as conv1 + the register-streamed tail, else None."""
-        if not FUSED_BOTTLENECK or not _fused_fits(x, self.cout):
-            return None
-        if self.l1 and x.shape[2] == (64 if self.code == ops.F16X3 else 96) and x.shape[1] % 2 == 0:   # 2-row tiles
-            return 'l1'
-        if self.l2 and x.shape[2] == 32 and x.shape[1] % 4 == 0:
-            return 'l2'
-        if self.l3 and x.shape[2] == 16 and x.shape[1] % 8 == 0:
-            return 'l3'
-        split = self.code == ops.F16X3   # (the split tails: 256x256 maps only)
-        if self.l3 and x.shape[2] == 24 and x.shape[1] % 6 == 0 and TAIL_W24 and not split:   # R152@384 (configs[4])
-            return 'l3w'
-        if self.l2 and x.shape[2] == 48 and x.shape[1] % 2 == 0 and TAIL_W24 and not split:   # layer2 at 384x384
-            return 'l2w'
-        return None
+            self.packs['s2_tail_next'] = pack_s2_tail_stream(c2.w, self.dual.w, self.chain.w)
 
     def link_layer(self, first):
         """Chain this last identity block's tail with the next layer's first block's conv1 (1x1 / stride 1,
         C -> 2 P: posu_bottleneck_tail_stream_chain_fwd): split fp16 layers 1-3, bf16 / fp16 layers 2-3
         (CHAIN_LAYERS_2B)."""
-        tails = (self.l1 or self.l2 or self.l3) if self.code == ops.F16X3 else (
-            CHAIN_LAYERS_2B and self.code in (ops.BF16, ops.F16) and (self.l2 or self.l3))
-        if not (tails and first.dual is not None):
+        if not (self._chains('layer') and (self.code in _SPLIT or CHAIN_LAYERS_2B) and first.dual is not None):
             return
         c1n = first.convs[0]
         planes = self.convs[1].cout
         if c1n.k == 1 and c1n.stride == 1 and c1n.cout == 2 * planes and tuple(c1n.w.shape)[1] == self.convs[0].w.shape[1]:
             self.xchain = c1n
-            self.wsx = pack_tail_stream(self.convs[1].w, self.convs[2].w, c1n.w)
-
-    def run(self, x, code, out=None, t1=None, chain_out=False, t1n_out=None):
-        """-> (y, t1n): t1n = the next block's conv1 output when this block's tail is chained
-        (CHAINED_TAILS; chain_out: the last block of a layer chaining the next layer's first conv1,
-        CHAIN_LAYERS), else None; t1 = this block's conv1 output from the previous block's
-        chained tail (None: computed here)."""
-        kind = self._tail_kind(x)
-        if kind is None:
-            if t1 is not None:
-                if self.dual is None:
-                    raise RuntimeError('a chained conv1 output handed to a block without a streamed tail')
-                # the first block of a layer whose conv1 the previous layer's last tail computed
-                return self.dual(self.convs[1](t1, code), x, code, out=out), None
-            if self.wsdn is not None and CHAINED_TAILS and self._down_tail_ok(x):
-                c1, c2 = self.convs
-                n1 = self.chain
-                return ops.bottleneck_down_tail_stream_nhwc(c1(x, code), x, self.wsdn, c2.scale, c2.shift, self.dscale,
-                                                            self.dual.shift, code, s1n=n1.scale, b1n=n1.shift, out=out)
-            if self.ws2n is not None and CHAINED_TAILS and S2_CHAIN and self._s2_tail_ok(x):
-                c1, c2 = self.convs
-                n1 = self.chain
-                return ops.bottleneck_s2_tail_next_nhwc(c1(x, code), x, self.ws2n, c2.scale, c2.shift, self.dual.shift,
-                                                        n1.scale, n1.shift, code, out=out)
-            return self(x, code, out=out), None
-        c1, c2, c3 = self.convs
-        if t1 is None:
-            t1 = c1(x, code)
-        if chain_out and self.xchain is not None and CHAINED_TAILS and CHAIN_LAYERS and \
-                kind in (('l1', 'l2', 'l3') if self.code == ops.F16X3 else ('l2', 'l3')):
-            n1 = self.xchain
-            return ops.bottleneck_tail_stream_chain_nhwc(t1, x, self.wsx, c2.scale, c2.shift, c3.scale, c3.shift,
-                                                         n1.scale, n1.shift, code, out=out, t1n=t1n_out)
-        if self.chain is not None and CHAINED_TAILS and (kind != 'l3w' or TAIL_W24_CHAIN):
-            n1 = self.chain
-            return ops.bottleneck_tail_stream_next_nhwc(t1, x, self.wsn, c2.scale, c2.shift, c3.scale, c3.shift,
-                                                        n1.scale, n1.shift, code, out=out)
-        return ops.bottleneck_tail_stream_nhwc(t1, x, self.wst, c2.scale, c2.shift, c3.scale, c3.shift, code,
-                                               out=out), None
-
-    def _down_tail_ok(self, x):
-        """Split layer1's first block runs conv1 + the down tail (SPLIT_TAILS)."""
-        return (self.wsd is not None and FUSED_BOTTLENECK and _fused_fits(x, self.cout) and x.shape[1] % 2 == 0 and
-                (x.shape[2] == 64 and self.code == ops.F16X3 and SPLIT_TAILS or
-                 x.shape[2] == 96 and self.code != ops.F16X3 and TAIL_W96))
-
-    def _s2_tail_ok(self, x):
-        """layer2's first block runs conv1 + the strided tail (S2_TAIL)."""
-        return (self.ws2 is not None and S2_TAIL and FUSED_BOTTLENECK and _fused_fits(x, self.cout) and
-                x.shape[2] == 64 and x.shape[1] % 8 == 0)
-
-    def _tail_shape(self, c, p, cm):
-        """An identity Bottleneck C -> P -> P -> C (1x1, 3x3 / 1 / pad 1, 1x1) whose packs hold cm
-        stored halves per logical k."""
-        c1, c2, c3 = self.convs
-        return (c1.k == 1 and c1.stride == 1 and tuple(c1.w.shape) == (p, c * cm) and
-                c2.k == 3 and c2.stride == 1 and c2.pad == 1 and tuple(c2.w.shape) == (p, 9 * p * cm) and
-                c3.k == 1 and c3.stride == 1 and tuple(c3.w.shape) == (c, p * cm))
-
-    def _layer1_shape(self, cm=1):
-        return self._tail_shape(256, 64, cm)
-
-    def _layer2_shape(self, cm=1):
-        return self._tail_shape(512, 128, cm)
-
-    def _layer3_shape(self, cm=1):
-        return self._tail_shape(1024, 256, cm)
-
-    def _fusable_shape(self):
-        c1, c2, c3 = self.convs
-        return (c1.k == 1 and c1.stride == 1 and c1.cout == 64 and c1.w.shape == (64, 256) and
-                c2.k == 3 and c2.stride == 1 and c2.pad == 1 and c2.cout == 64 and c2.w.shape == (64, 576) and
-                c3.k == 1 and c3.stride == 1 and c3.cout == 256)
+            self.packs['tail_layer'] = pack_tail_stream(self.convs[1].w, self.convs[2].w, c1n.w)
 
     @property
     def cout(self):
         return self.dual.cout if self.dual is not None else self.convs[-1].cout
 
-    def __call__(self, x, code, out=None):
-        y = x
-        fits = _fused_fits(x, self.cout)
-        if self.w3d is not None and FUSED_BOTTLENECK and fits and x.shape[2] == 64 and x.shape[3] == 64:
-            c1, c2 = self.convs
-            return ops.bottleneck_down_nhwc(x, c1.w, c1.scale, c1.shift, c2.w, c2.scale, c2.shift, self.w3d,
-                                            self.dual.shift, code, out=out)
-        if self._down_tail_ok(x):
-            c1, c2 = self.convs
-            return ops.bottleneck_down_tail_stream_nhwc(c1(x, code), x, self.wsd, c2.scale, c2.shift, self.dscale,
-                                                        self.dual.shift, code, out=out)[0]
-        if self._s2_tail_ok(x):
-            c1, c2 = self.convs
-            return ops.bottleneck_s2_tail_nhwc(c1(x, code), x, self.ws2, c2.scale, c2.shift, self.dual.shift, code,
-                                               out=out)
+    def _at(self, kernel, x):
+        """The _GEOMETRY row under which this block runs `kernel` on x [N, H, W, C], or None: the block has
+        the kernel's packs, the fused kernels are on (FUSED_BOTTLENECK) and address x and y, and a row of
+        this dtype, its per-call switch on, has x's width and divides its rows."""
+        g = _GEOMETRY[kernel]
+        if not (kernel == self.kind or kernel in self.packs) or not FUSED_BOTTLENECK or \
+                x.shape[3] != g.conv1[1] * ops.cmul(self.code) or not _fused_fits(x, self.cout):
+            return None
+        return next((a for a in g.at if self.code in a.codes and x.shape[2] == a.width and
+                     x.shape[1] % a.rows == 0 and _on(a.live)), None)
+
+    def select(self, x, t1=False, chain_out=False, chain=True):
+        """-> (variant, chained): the launches run() makes for the input x (only its shape and dtype are
+        read; nothing is launched or allocated).  t1: this block's conv1 output is handed in (the previous
+        tail chained it); chain_out: this is a layer's last block, asked for the next layer's first conv1;
+        chain = False suppresses chaining.  chained: None, 'next' or 'layer' -- the extra output."""
+        chain = chain and CHAINED_TAILS
+        at = self._at(self.kind, x) if self.kind is not None else None
+        if at is not None:
+            if chain and chain_out and CHAIN_LAYERS and self.xchain is not None and 'layer' in at.chains:
+                return 'tail', 'layer'
+            return 'tail', ('next' if chain and self.chain is not None and 'next' in at.chains else None)
+        if t1:
+            if self.dual is None:
+                raise RuntimeError('a chained conv1 output handed to a block without a streamed tail')
+            return 'dual', None   # the first block of a layer whose conv1 the previous layer's last tail computed
+        for variant in ('fused_down', 'down_tail', 's2_tail'):
+            at = self._at(variant, x)
+            if at is not None:
+                nxt = (chain and variant + '_next' in self.packs and 'next' in at.chains and
+                       (S2_CHAIN or variant != 's2_tail'))
+                return variant, ('next' if nxt else None)
         if self.dual is not None:
-            for c in self.convs:
-                y = c(y, code)
-            return self.dual(y, x, code, out=out)
-        if self.w3f is not None and FUSED_BOTTLENECK and fits and x.shape[2] == 64:
-            c1, c2, c3 = self.convs
-            return ops.bottleneck_nhwc(x, self.w1f, c1.scale, c1.shift, c2.w, c2.scale, c2.shift, self.w3f, c3.scale,
-                                       c3.shift, code, out=out)
-        if self._tail_kind(x) is not None:
-            c1, c2, c3 = self.convs
-            return ops.bottleneck_tail_stream_nhwc(c1(x, code), x, self.wst, c2.scale, c2.shift, c3.scale, c3.shift,
-                                                   code, out=out)
+            return 'dual', None
+        return ('fused' if self._at('fused', x) is not None else 'convs'), None
+
+    def run(self, x, code, out=None, t1=None, chain_out=False, t1n_out=None, chain=True):
+        """-> (y, t1n): t1n = the conv1 output this block's tail computed for the next block (CHAINED_TAILS)
+        or, chain_out, for the next layer's first block (CHAIN_LAYERS; into t1n_out), else None; t1 = this
+        block's conv1 output from the previous block's chained tail (None: computed here)."""
+        variant, chained = self.select(x, t1 is not None, chain_out, chain)
+        cs = self.convs
+        if variant == 'tail':
+            c2, c3 = cs[1:]
+            if t1 is None:
+                t1 = cs[0](x, code)
+            if chained == 'layer':
+                n1 = self.xchain
+                return ops.bottleneck_tail_stream_chain_nhwc(t1, x, self.packs['tail_layer'], c2.scale, c2.shift,
+                                                             c3.scale, c3.shift, n1.scale, n1.shift, code, out=out,
+                                                             t1n=t1n_out)
+            if chained == 'next':
+                n1 = self.chain
+                return ops.bottleneck_tail_stream_next_nhwc(t1, x, self.packs['tail_next'], c2.scale, c2.shift,
+                                                            c3.scale, c3.shift, n1.scale, n1.shift, code, out=out)
+            return ops.bottleneck_tail_stream_nhwc(t1, x, self.packs['tail'], c2.scale, c2.shift, c3.scale, c3.shift,
+                                                   code, out=out), None
+        if variant == 'fused':
+            c1, c2, c3 = cs
+            w1f, w3f = self.packs['fused']
+            return ops.bottleneck_nhwc(x, w1f, c1.scale, c1.shift, c2.w, c2.scale, c2.shift, w3f, c3.scale, c3.shift,
+                                       code, out=out), None
+        if variant == 'fused_down':
+            c1, c2 = cs
+            return ops.bottleneck_down_nhwc(x, c1.w, c1.scale, c1.shift, c2.w, c2.scale, c2.shift,
+                                            self.packs['fused_down'], self.dual.shift, code, out=out), None
+        if variant == 'down_tail':
+            c1, c2 = cs
+            s1n, b1n = (self.chain.scale, self.chain.shift) if chained else (None, None)
+            return ops.bottleneck_down_tail_stream_nhwc(
+                c1(x, code), x, self.packs['down_tail_next' if chained else 'down_tail'], c2.scale, c2.shift,
+                self.dscale, self.dual.shift, code, s1n=s1n, b1n=b1n, out=out)
+        if variant == 's2_tail':
+            c1, c2 = cs
+            if chained:
+                n1 = self.chain
+                return ops.bottleneck_s2_tail_next_nhwc(c1(x, code), x, self.packs['s2_tail_next'], c2.scale, c2.shift,
+                                                        self.dual.shift, n1.scale, n1.shift, code, out=out)
+            return ops.bottleneck_s2_tail_nhwc(c1(x, code), x, self.packs['s2_tail'], c2.scale, c2.shift,
+                                               self.dual.shift, code, out=out), None
+        if variant == 'dual':
+            return self.dual(cs[1](cs[0](x, code) if t1 is None else t1, code), x, code, out=out), None
         res = self.down(x, code) if self.down is not None else x
-        for c in self.convs[:-1]:
+        y = x
+        for c in cs[:-1]:
             y = c(y, code)
-        return self.convs[-1](y, code, residual=res, out=out)
+        return cs[-1](y, code, residual=res, out=out), None
+
+    def __call__(self, x, code, out=None):
+        """The block alone, unchained: y."""
+        return self.run(x, code, out=out, chain=False)[0]
 
 
 class _Deconv:
@@ -669,38 +670,30 @@ class PoseResNetPlan:
                 out=out, out_hw=(x.shape[1], x.shape[2]), tile=t))
         return self.stem(x, code)
 
-    def _stage_early(self, x, out=None, keep=None, t1_out=None, nl=2):
-        """stem -> maxpool -> layer1 [-> layer2] (nl layers; out: the last one's output slice, keep: layer1
-        output slice to fill when nl = 2); each layer's last tail hands the next layer's first block its
-        conv1 output as in the whole-batch run (CHAIN_LAYERS): inside the slice, and the last early
-        layer's into t1_out (the slice of a whole-batch buffer the next layer takes).  Returns (last early
-        layer's out, layer1 out, t1_out if the last tail filled it)."""
-        code = self.code
-        x = self.stem_pool(x)
-        t1 = None
+    def _run_layers(self, x, lo, hi, t1=None, out=None, keep=None, t1_out=None):
+        """Layers lo .. hi - 1 block by block -> (the last one's output, layer1's or None, t1).  A chained
+        tail hands the next block its conv1 output (CHAINED_TAILS), a layer's last tail the next layer's
+        first block (CHAIN_LAYERS): t1 is the first block's, from the walk before, and the returned t1 the
+        one the walk's last tail put into t1_out (the slice of a whole-batch buffer the next walk takes; given
+        only where that tail chains), else None.  out / keep: the slices the last layer's / layer1's output
+        go to."""
         x1 = None
-        for li in range(nl):
+        for li in range(lo, hi):
             layer = self.layers[li]
+            final = li == hi - 1
             for bi, blk in enumerate(layer):
                 last = bi == len(layer) - 1
-                dst = out if li == nl - 1 else (keep if li == 0 else None)
-                x, t1 = blk.run(x, code, out=dst if last else None, t1=t1,
-                                chain_out=last and (li < nl - 1 or t1_out is not None),
-                                t1n_out=t1_out if li == nl - 1 and last else None)
+                dst = (out if final else keep if li == 0 else None) if last else None
+                x, t1 = blk.run(x, self.code, out=dst, t1=t1, chain_out=last and (not final or t1_out is not None),
+                                t1n_out=t1_out if last and final else None)
             if li == 0:
                 x1 = x
         return x, x1, t1
 
-    @staticmethod
-    def _run_layer(layer, x, code, out=None):
-        """The blocks of one layer in order (out: the last block's output buffer); chained
-        streamed tails hand the next block its conv1 output."""
-        t1 = None
-        for bi, blk in enumerate(layer):
-            x, t1 = blk.run(x, code, out=out if bi == len(layer) - 1 else None, t1=t1)
-        if t1 is not None:
-            raise RuntimeError('the last block of a layer produced a chained conv1 output')
-        return x
+    def _stage_early(self, x, out=None, keep=None, t1_out=None, nl=2):
+        """stem -> maxpool -> layer1 [-> layer2] (nl layers; out: the last one's output slice, keep: layer1
+        output slice to fill when nl = 2).  Returns whether the last tail filled t1_out."""
+        return self._run_layers(self.stem_pool(x), 0, nl, out=out, keep=keep, t1_out=t1_out)[2] is not None
 
     def _last_deconv_head(self, x, keep_f, hm_out=None, f_out=None):
         """Last deconv (+BN+ReLU) and the 1x1 head, fused into one launch when possible."""
@@ -721,10 +714,6 @@ class PoseResNetPlan:
             x = dc(x, code)
         return self._last_deconv_head(x, keep_f, hm_out=hm_out, f_out=f_out)
 
-    @staticmethod
-    def _block_cout(blk):
-        return blk.cout
-
     def default_chunks(self):
         """The depth-first slices run(chunks=None) takes: CHUNKS_F16X3 for the split dtype, else 1."""
         return CHUNKS_F16X3 if self.code == ops.F16X3 else 1
@@ -744,7 +733,7 @@ class PoseResNetPlan:
                 self._refine_in_context(x, chunks, keep_features)
         return out
 
-    def _refine_in_context(self, x, chunks, keep_features, within=None, top=None, forwards=6):
+    def _refine_in_context(self, x, chunks, keep_features, within=0.25, top=3, forwards=6):
         """Second tuning stage: for every geometry of this forward whose best per-launch
         candidates lie within 25 % of each other, run the whole forward with each of its top
         three and keep the one whose launches of that geometry took least INSIDE the forward
@@ -754,7 +743,8 @@ class PoseResNetPlan:
         3x3 took 53 us on two tiles in isolation and 62 vs 75 us on them in the graph
         (profiles/r04/replay_breakdown*.txt).  (Round 4 compared whole-forward times, whose
         run-to-run spread -- ~0.5 % of 2.5 ms -- is as large as the differences it had to
-        resolve: deconv1 went to a tile 15 us slower in one tuning, profiles/r05.)"""
+        resolve: deconv1 went to a tile 15 us slower in one tuning, profiles/r05.)  within / top: the
+        candidate window; a wider one measured no gain (2.329 / 2.335 vs 2.325 / 2.317 ms, call r6ak)."""
         def forward_ms(key):
             self.run(x, chunks=chunks, keep_features=keep_features)
             torch.cuda.synchronize()
@@ -767,8 +757,6 @@ class PoseResNetPlan:
             finally:
                 _Tuner.probe, _Tuner.probe_events = None, []
             return ms[len(ms) // 2] if ms else float('inf')
-        within = REFINE_WITHIN if within is None else within
-        top = REFINE_TOP if top is None else top
         for key in list(_Tuner.seen):
             times = _TUNE_TIMES.get(key)
             if not times or key not in _TUNE_CACHE:
@@ -800,14 +788,7 @@ class PoseResNetPlan:
             chunks = self.default_chunks()
         n = x.shape[0]
         if chunks <= 1 or n % chunks or len(self.deconvs) < 2:
-            x = self.stem_pool(x)
-            x1 = None
-            t1 = None   # a conv1 output handed across a layer boundary (CHAIN_LAYERS)
-            for li, layer in enumerate(self.layers):
-                for bi, blk in enumerate(layer):
-                    x, t1 = blk.run(x, code, t1=t1, chain_out=bi == len(layer) - 1 and li + 1 < len(self.layers))
-                if li == 0:
-                    x1 = x
+            x, x1, t1 = self._run_layers(self.stem_pool(x), 0, len(self.layers))
             if t1 is not None:
                 raise RuntimeError('the last layer produced a chained conv1 output')
             for dc in self.deconvs[:-1]:
@@ -827,40 +808,30 @@ class PoseResNetPlan:
         he, we = hp, wp
         for _ in range(el - 1):                                  # layers 2.. halve the grid
             he, we = (he - 1) // 2 + 1, (we - 1) // 2 + 1
-        x2 = torch.empty((n, he, we, self._block_cout(self.layers[el - 1][-1]) * cm), dtype=dt, device=dev)
-        x1 = x2 if el == 1 else (torch.empty((n, hp, wp, self._block_cout(self.layers[0][-1]) * cm), dtype=dt,
+        tail = self.layers[el - 1][-1]   # the last early block
+        x2 = torch.empty((n, he, we, tail.cout * cm), dtype=dt, device=dev)
+        x1 = x2 if el == 1 else (torch.empty((n, hp, wp, self.layers[0][-1].cout * cm), dtype=dt,
                                              device=dev) if keep_features else None)
-        # the next layer's first conv1, computed by the last early layer's tail chunk by chunk
-        # (CHAIN_LAYERS), else None
-        nc1 = self.layers[el][0].convs[0] if len(self.layers) > el and self.layers[el][0].convs else None
-        t1 = (torch.empty((n, he, we, nc1.cout * cm), dtype=dt, device=dev)
-              if nc1 is not None and self.layers[el - 1][-1].xchain is not None else None)
+        # the next layer's first conv1 over the whole batch, where the last early tail computes it chunk by
+        # chunk (CHAIN_LAYERS; only an identity block chains, so its input has the shape of its output, a
+        # chunk of x2), else None
+        t1 = (torch.empty((n, he, we, tail.xchain.cout * cm), dtype=dt, device=dev)
+              if tail.select(x2[:c], chain_out=True) == ('tail', 'layer') else None)
         chained = []
-        ce = chunks if CHUNK_EARLY else 1
-        c = n // ce
-        for k in range(ce):
+        for k in range(chunks):
             sl = slice(k * c, (k + 1) * c)
-            _, _, t1k = self._stage_early(x[sl], out=x2[sl], keep=None if (x1 is None or el == 1) else x1[sl],
-                                          t1_out=None if t1 is None else t1[sl], nl=el)
-            chained.append(t1k is not None)
+            chained.append(self._stage_early(x[sl], out=x2[sl], keep=None if (x1 is None or el == 1) else x1[sl],
+                                             t1_out=None if t1 is None else t1[sl], nl=el))
         if any(chained) != all(chained):
             raise RuntimeError('the chunks of one batch took different tails')
-        t1 = t1 if all(chained) else None
-        y = x2
-        for li in range(el, len(self.layers)):
-            layer = self.layers[li]
-            for bi, blk in enumerate(layer):
-                last = bi == len(layer) - 1
-                y, t1 = blk.run(y, code, t1=t1, chain_out=last and li + 1 < len(self.layers))
+        y, _, t1 = self._run_layers(x2, el, len(self.layers), t1=t1 if all(chained) else None)
         if t1 is not None:
             raise RuntimeError('the last layer produced a chained conv1 output')
         y = self.deconvs[0](y, code)
         hf, wf = y.shape[1] * 2 ** (len(self.deconvs) - 1), y.shape[2] * 2 ** (len(self.deconvs) - 1)
         hm = torch.empty((n, self.njoints, hf, wf), dtype=torch.float32, device=dev)
         f = (torch.empty((n, hf, wf, self.deconvs[-1].cout * cm), dtype=dt, device=dev) if keep_features else None)
-        cl = (LATE_CHUNKS if LATE_CHUNKS > 0 and n % LATE_CHUNKS == 0 else chunks) if CHUNK_LATE else 1
-        c = n // cl
-        for k in range(cl):
+        for k in range(chunks):
             sl = slice(k * c, (k + 1) * c)
             self._stage_late(y[sl], hm_out=hm[sl], f_out=None if f is None else f[sl], keep_f=f is not None)
         return hm, (x1 if keep_features else None), f

@@ -364,10 +364,10 @@ def test_plan_with_fused_bottlenecks_matches_unfused_plan(cuda, precision):
     net.load_state_dict(syn.synthetic_state_dict(net.state_dict(), seed=0, bn_stats=syn.load_bn_stats(50, 256)))
     net = net.to(cuda).eval()
     plan = net.plan(cuda)
-    assert sum(b.w3f is not None for b in plan.layers[0]) == 2   # layer1 blocks 1 and 2
-    assert plan.layers[0][0].w3d is not None                     # layer1 block 0
-    assert [b.l2 for b in plan.layers[1]] == [False, True, True, True]   # layer2's identity blocks
-    assert [b.l3 for b in plan.layers[2]] == [False] + [True] * 5        # layer3's identity blocks
+    assert sum('fused' in b.packs for b in plan.layers[0]) == 2   # layer1 blocks 1 and 2
+    assert 'fused_down' in plan.layers[0][0].packs                # layer1 block 0
+    assert [b.kind == 'l2' for b in plan.layers[1]] == [False, True, True, True]   # layer2's identity blocks
+    assert [b.kind == 'l3' for b in plan.layers[2]] == [False] + [True] * 5        # layer3's identity blocks
     views = [v.to(cuda) for v in syn.synthetic_views(4, 2, 256, seed=12)]
     saved = P.FUSED_BOTTLENECK
     try:
@@ -397,7 +397,8 @@ def test_plan_strided_tail_is_bit_identical_to_two_launches(cuda, precision):
     net.load_state_dict(syn.synthetic_state_dict(net.state_dict(), seed=0, bn_stats=syn.load_bn_stats(50, 256)))
     net = net.to(cuda).eval()
     plan = net.plan(cuda)
-    assert plan.layers[1][0].ws2 is not None and all(b.ws2 is None for b in plan.layers[2] + plan.layers[3])
+    assert 's2_tail' in plan.layers[1][0].packs
+    assert not any('s2_tail' in b.packs for b in plan.layers[2] + plan.layers[3])
     views = [v.to(cuda) for v in syn.synthetic_views(4, 2, 256, seed=13)]
     saved = P.S2_TAIL
     try:
@@ -583,17 +584,17 @@ def test_split_plan_tails_are_bit_identical_to_conv_launches(cuda):
         with torch.no_grad():
             P.SPLIT_TAILS = True
             plan = P.PoseResNetPlan(net, ops.F16X3)
-            assert [b.l1 for b in plan.layers[0]] == [False, True, True]
-            assert [b.l2 for b in plan.layers[1]] == [False, True, True, True]
-            assert [b.l3 for b in plan.layers[2]] == [False] + [True] * 5
-            assert plan.layers[0][0].wsdn is not None      # layer1 block 0 on the down tail, chained
+            assert [b.kind == 'l1' for b in plan.layers[0]] == [False, True, True]
+            assert [b.kind == 'l2' for b in plan.layers[1]] == [False, True, True, True]
+            assert [b.kind == 'l3' for b in plan.layers[2]] == [False] + [True] * 5
+            assert 'down_tail_next' in plan.layers[0][0].packs      # layer1 block 0 on the down tail, chained
             # the last tail of layers 1-3 chains the next layer's first conv1 (CHAIN_LAYERS)
             assert [layer[-1].xchain is not None for layer in plan.layers] == [True, True, True, False]
             assert [b.chain is not None for b in plan.layers[0]] == [True, True, False]
             hm1, x11, f1 = plan.run(plan.pack_input(views))
             P.SPLIT_TAILS = False
             plan0 = P.PoseResNetPlan(net, ops.F16X3)
-            assert not any(b.l1 or b.l2 or b.l3 for layer in plan0.layers for b in layer)
+            assert all(b.kind is None for layer in plan0.layers for b in layer)
             hm0, x10, f0 = plan0.run(plan0.pack_input(views))
     finally:
         P.SPLIT_TAILS = saved
