@@ -150,15 +150,21 @@ int posu_nhwc_to_nchw_f32(int dtype, const void* x, int N, int H, int W, int C,
  *     cfg 0: 256x64, 1: 128x64, 2: 64x64, 3: 128x128, 4: 64x128 (four waves),
  *         5: 256x256, 6: 256x128 (eight waves);
  *     variant 1: single-slot LDS ring (cfg 0-4), 2: three-slot ring (cfg != 5);
- *     + 32 (bf16 / f16): the persistent K-tile stream;
+ *     + 32 (bf16 / f16): the persistent K-tile stream (cfg 0 has none and runs its plain ring);
+ *        the other dtypes, and outputs of 2 GiB or more, ignore the bit;
  *     23 / 31 (bf16 / f16): 256x256 / 256x128 with waves 4-7 staggered by half a K-tile;
  *     7 / 15 (bf16 / f16, ABI 11): 128x128 with eight staggered waves (2x4 / 4x2 wave grids);
- *     39 (bf16 / f16, ABI 13, NHWC outputs): 128x128 with two K groups of four waves (each group
+ *     39 (2-byte dtypes, ABI 13, NHWC outputs): 128x128 with two K groups of four waves (each group
  *        sums every other K-tile over the whole tile, the halves added in LDS at the end: a
  *        different K order, so not bit-identical to the other tiles);
  *     split fp16 (POSU_F16X3): 7 / 15 unstaggered; 31 (ABI 16) staggered, the lagging waves holding a
- *        K-tile's third product hi(w).lo(x) across the barrier; 47 / 55 (ABI 16) the staggered
- *        128x128 eight-wave tiles (2x4 / 4x2 wave grids).
+ *        K-tile's third product hi(w).lo(x) across the barrier; 47 / 55 (ABI 16, this dtype only) the
+ *        staggered 128x128 eight-wave tiles (2x4 / 4x2 wave grids).
+ *   An id that exists but has no kernel for the launch runs the heuristic's tile instead: a tile
+ *   wider than CoutPad divides into (128 for cfg 3 / 4 / 6 and 7 / 15 / 31 / 39 / 47 / 55, 256 for
+ *   cfg 5 and 23), 7 / 15 / 23 / 31 / 39 in f32, 23 in split fp16.  Refused ("tile must be"): every
+ *   other id, 47 / 55 outside split fp16 among them.  The one table behind all of this is kTiles
+ *   in csrc/conv_igemm.hip.
  *   The tile only changes speed (every configuration but 39 computes the same sums in the same
  *   K order); the Python plan picks it per layer by timing every admissible
  *   configuration once (PoseResNetPlan.autotune).  The library keeps no mutable state:

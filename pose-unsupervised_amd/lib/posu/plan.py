@@ -123,7 +123,11 @@ def _tile_candidates(cout, code=None, ksplit=False):
     short-K layers: more blocks per CU), cfg + 16 = three-slot ring (two K-tiles in flight),
     cfg + 32 = persistent K-tile stream (epilogue stores overlap the next tile's fetch),
     23 / 31 = 256x256 / 256x128 with waves 4-7 staggered by half a K-tile, 7 / 15 = 128x128 with
-    eight staggered waves."""
+    eight waves (staggered in bf16 / f16, unstaggered in split fp16, whose staggered twins are
+    47 / 55), 39 = 128x128 with two K groups.  The library's table (kTiles, csrc/conv_igemm.hip)
+    says what every id runs per dtype; an id it has no kernel for in a dtype (the + 32 bit and
+    7 / 15 / 23 / 31 / 39 in f32) runs the id without the bit or the heuristic's tile, which the
+    f32 lists below rely on."""
     cpad = (cout + 63) // 64 * 64
     c = [0, 1, 2]
     if cpad % 128 == 0:

@@ -49,6 +49,34 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert st == 1 and 'inference-only' in _native.last_error()
 
 
+def test_unknown_tiles_are_refused_without_a_gpu():
+    """The four entry points with a `tile` argument refuse every id the tile table (conv_igemm.hip,
+    kTiles) has no row for in the launch's dtype: the holes of cfg + 8 * variant (+ 32) for every
+    dtype, and 47 / 55 -- the split dtype's staggered 128x128 tiles -- for every other dtype.  Only
+    refusals are checked: an accepted id would go on to launch."""
+    lib = _native.load()
+    p = ctypes.c_void_p(16)
+    every, plain = (_native.BF16, _native.F16, _native.F16X3, _native.F32), (_native.BF16, _native.F16, _native.F32)
+    calls = [
+        (every, lambda dt, t: lib.posu_conv2d_fwd(dt, p, 1, 8, 8, 64, p, 64, 3, 3, 1, 1, None, None, None, 1, p,
+                                                  8, 8, t, None)),
+        (every, lambda dt, t: lib.posu_conv1x1_dual_fwd(dt, p, 1, 8, 8, 64, p, 8, 8, 64, 1, p, 64, None, None, 1,
+                                                        p, t, None)),
+        (every, lambda dt, t: lib.posu_deconv4x4s2_fwd(dt, p, 1, 8, 8, 64, p, 64, None, None, 1, p, t, None)),
+        # (the data gradient does not take the split dtype)
+        (plain, lambda dt, t: lib.posu_conv2d_dgrad_tile(dt, p, 1, 8, 8, 64, p, 64, 3, 3, 1, 1, None, p, 8, 8, t,
+                                                         None)),
+    ]
+    for n, (dtypes, call) in enumerate(calls):
+        for dt in dtypes:
+            bad = (13, 21, 29, 45, 63, 64, -2) + ((47, 55) if dt != _native.F16X3 else ())
+            for t in bad:
+                assert call(dt, t) == 1, (n, dt, t)
+                err = _native.last_error()
+                assert 'tile must be' in err and ' %d,' % t not in err + ',', (n, dt, t, err)
+                assert n != 3 or 'unknown tile' in err
+
+
 def test_split_pack_layout():
     """packing.to_split: per 32-k block [hi 32 | lo 32], hi = fp16(v 2^e), lo = fp16(v 2^e - hi)."""
     torch.manual_seed(3)

@@ -392,8 +392,9 @@ def test_every_tile_configuration_matches_torch(cuda, cfg, code):
 def test_invalid_tile_is_refused(cuda):
     x = torch.zeros(1, 8, 8, 64, device=cuda, dtype=torch.bfloat16)
     w = torch.zeros(64, 64, device=cuda, dtype=torch.bfloat16)
-    # (7 / 15: the 128x128 eight-wave tiles since round 4; 39 round 5; 47 / 55 split fp16, round 6)
-    for bad in (63, 29, 64, 70, 40 + 5):
+    # (7 / 15: the 128x128 eight-wave tiles since round 4; 39 round 5; 47 / 55 exist for split fp16
+    # only, round 6, and are refused here: the call is bf16)
+    for bad in (63, 29, 64, 70, 40 + 5, 47, 55):
         with pytest.raises(RuntimeError, match='tile must be'):
             ops.conv2d_nhwc(x, w, 64, 1, 1, 1, 0, None, None, None, False, BF16, tile=bad)
 
@@ -441,7 +442,7 @@ def test_staggered_tiles_bit_exact_vs_two_slot(cuda, code):
     """The staggered loops (tiles 23 / 31: waves 4-7 half a K-tile behind) keep each
     accumulator's K order, so their outputs equal the two-slot loops (tiles 5 / 6) bit for
     bit: 3x3 + residual (ragged M), strided 1x1, ConvTranspose(4, s2) and the two-source
-    Bottleneck tail.  (f32 has no staggered loop: its 23 / 31 run as 5 / 6.)"""
+    Bottleneck tail.  (f32 has no staggered loop: its 23 / 31 run the heuristic's tile.)"""
     dt = ops.torch_dtype(code)
     g = torch.Generator(device=cuda).manual_seed(5)
     sc = torch.rand(256, device=cuda, generator=g) + 0.5
