@@ -73,7 +73,8 @@ const char* posu_last_error(void);
  * sources of the batched deconv packing (the strided 3x3 convs' sub-pixel data gradient), the
  * Adam step (posu_adam_step); 16 (round 6) the split-fp16 dtype in the streamed Bottleneck tails
  * (posu_bottleneck_tail_stream_fwd / _next_fwd, layer1 / layer2 / layer3 at 256x256) and the
- * downsampling first-block tail (posu_bottleneck_down_tail_stream_fwd).  The
+ * downsampling first-block tail (posu_bottleneck_down_tail_stream_fwd).  The RPSM entry points
+ * (posu_rpsm_*) are additive to 16: new symbols only, the revision does not move.  The
  * ctypes binding refuses a library of another revision. */
 int posu_abi_version(void);
 
@@ -521,6 +522,83 @@ int posu_reproject(const double* M, const double* intr, const double* xy, const 
                    int G, int V, int J, int undistort, double* proj, unsigned char* res_vis,
                    void* stream);
 
+/* ------------------------------------------------------------------- RPSM */
+/* The recursive pictorial structure model (lib/multiviews/pictorial.py, driven by
+ * run/test/test_rpsm.py): multi-view heatmaps -> 3-D pose by max-product inference over the
+ * skeleton tree on a grid of N = nbins^3 bins, refined RECUR_DEPTH times on a small grid around
+ * every joint.  These entry points are additive to ABI 16 (nothing older changes).  fp64
+ * throughout, in the reference's operation order, compiled without fused multiply-adds: the
+ * results are discrete decisions.  Limits: 1 <= V <= 8, 2 <= J <= 32, 2 <= nbins, N <= 4096,
+ * H == W (the reference's interpolator only works for square heatmaps).
+ *
+ * The tree (multiviews/body.py) is three HOST int arrays, read during the call: parent [J]
+ * (root = -1), child_ptr [J + 1] and child_idx [J - 1] -- node n's children, in the order of
+ * its 'children' list, are child_idx[child_ptr[n] .. child_ptr[n + 1]).  Edge e (a row of the
+ * packed constraint) is the edge into child_idx[e].  Limb lengths are indexed by the child joint
+ * (the root's entry is ignored): a DEVICE f64 table [G, J], one row per group, where groups are
+ * inferred (posu_rpsm_infer, posu_rpsm_run); HOST double [J] for the mask builder.
+ * The packed constraint is uint32 [J - 1, ceil(N / 32), N]: bit (j & 31) of word [e][j / 32][i]
+ * allows child bin j under parent bin i (numpy.packbits, bitorder 'little', of row i; the word
+ * index outside the parent bin so that consecutive lanes read consecutive words).
+ * Bin order (compute_grid, pictorial.py:108-119; numpy meshgrid 'xy'): flat bin
+ * b = (a * nbins + bx) * nbins + c has coordinates (x[bx], y[a], z[c]). */
+
+/* Bytes posu_rpsm_run needs for G groups (-1: a shape outside the limits). */
+long long posu_rpsm_workspace_bytes(int G, int J, int first_nbins, int recur_nbins);
+/* compute_grid (pictorial.py:108-119) for `count` boxes: centers [count, 3] f64 ->
+ * grid [count, nbins^3, 3] f64, axis = linspace(-size/2, size/2, nbins) + center. */
+int posu_rpsm_grid(const double* centers, int count, double size, int nbins, double* grid, void* stream);
+/* compute_unary_term (pictorial.py:146-190): unary [G, J, N] f64 = sum over views of the bilinear
+ * sample (scipy RegularGridInterpolator on hmap.T, linear, 0 outside [0, H-1]) of heatmaps
+ * [G, V, J, H, W] f32 at the grid point projected by cameras.project_pose (cameras.py:25-54,
+ * avg_f), the crop affine and * [W, H] / (img_w, img_h).
+ *   cams:   [G, V, 20] f64 = R row-major [9], T [3], f = (fx + fy) / 2, cx, cy, k [3], p [2];
+ *   affine: [G, V, 2, 3] f64 = get_affine_transform(center, scale, 0, image_size);
+ *   grid:   [G, NG, N, 3] f64, NG = 1 (shared by the joints) or J. */
+int posu_rpsm_unary(const float* heatmaps, const double* cams, const double* affine, int G, int V,
+                    int J, int H, int W, double img_w, double img_h, const double* grid, int NG,
+                    int N, double* unary, void* stream);
+/* infer's forward pass (pictorial.py:36-65) on one grid level, one max-product launch per tree
+ * depth, deepest first.  For edge (p, c) and parent bin i: v_j = P[i, j] * energy[c][j] (a
+ * disallowed pair is a zero, not -inf), maxv[c][i] = max_j v_j, state[c][i] = the first j
+ * attaining it; energy[p] = ((unary[p] * maxv[c1]) * maxv[c2]) ... in children order.
+ *   P: mask != NULL: the packed constraint (above), shared by the groups;
+ *      mask == NULL: |norm(grid[p][i] - grid[c][j]) - limb[g][c]| <= tolerance
+ *      (compute_pairwise_constrain, pictorial.py:122-143), grid [G, NG, N, 3], limb DEVICE f64
+ *      [G, J] (every group its own limb lengths, as run/test/test_rpsm.py:123 computes them);
+ *   unary [G, J, N] f64 in; energy, maxv [G, J, N] f64 and state [G, J, N] int32 out (the root's
+ *   maxv / state rows are not written). */
+int posu_rpsm_infer(const double* unary, const int* parent, const int* child_ptr, const int* child_idx,
+                    const unsigned int* mask, const double* grid, int NG, const double* limb,
+                    double tolerance, int G, int J, int N, double* energy, double* maxv, int* state,
+                    void* stream);
+/* infer's back-tracking and get_loc_from_cube_idx (pictorial.py:68-105): the root takes the first
+ * argmax of its energy, every other joint state[joint][its parent's bin]; bins [G, J] int32 and
+ * pose [G, J, 3] f64 = the bins' grid coordinates (either may be NULL). */
+int posu_rpsm_backtrack(const double* energy, const int* state, const int* parent, const int* child_ptr,
+                        const int* child_idx, const double* grid, int NG, int G, int J, int N, int* bins,
+                        double* pose, void* stream);
+/* The packed constraint of every edge from grid [NG, N, 3] (NG = 1 or J): bit = |norm(g_p[i] -
+ * g_c[j]) - limb[c]| < thr[c] (strict != 0: compute_pairwise_constraint of
+ * run/test/generate_pairwise_constraints.py:60-95 on a centred grid, thr = 0.4 limb) or <= thr[c]
+ * (strict == 0: pictorial.py:122-143).  limb, thr: HOST double [J] by child joint.
+ * mask: the packed constraint [J - 1, ceil(N / 32), N] uint32. */
+int posu_rpsm_pairwise_mask(const double* grid, int NG, int N, const int* parent, const int* child_ptr,
+                            const int* child_idx, int J, const double* limb, const double* thr, int strict,
+                            unsigned int* mask, void* stream);
+/* rpsm (pictorial.py:214-250) for G groups, enqueued without a host synchronisation: level 1 on
+ * the grid_size box of first_nbins^3 bins at grid_centers [G, 3] with the packed constraint, then
+ * recur_depth refinements of recur_nbins^3 bins per joint on boxes of grid_size / first_nbins /
+ * recur_nbins^level with the on-the-fly constraint from limb (DEVICE f64 [G, J], a row per
+ * group).  G * J <= 65535 per call.  pose: [G, J, 3] f64; level_poses: NULL or
+ * [recur_depth + 1, G, J, 3] f64 (the pose after level 1 and after every refinement);
+ * workspace >= posu_rpsm_workspace_bytes(G, J, first_nbins, recur_nbins) bytes. */
+int posu_rpsm_run(const float* heatmaps, const double* cams, const double* affine, int G, int V, int J,
+                  int H, int W, double img_w, double img_h, const double* grid_centers, double grid_size,
+                  int first_nbins, int recur_nbins, int recur_depth, double tolerance, const double* limb,
+                  const unsigned int* mask, const int* parent, const int* child_ptr, const int* child_idx,
+                  void* workspace, long long workspace_bytes, double* pose, double* level_poses,
+                  void* stream);
 
 /* ----------------------------------------------------------- training path */
 /* BASELINE configs[3]: the data-parallel training step (run/pose2d/train.py +

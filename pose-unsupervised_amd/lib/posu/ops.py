@@ -535,3 +535,153 @@ def reproject(M, intr, xy, vis=None, undistort=True):
     call('posu_reproject', ptr(M.contiguous()), ptr(intr.contiguous()), ptr(xy), ptr(vis), g, v, j,
          int(bool(undistort)), ptr(proj), ptr(res), stream_of(xy.device))
     return proj, res
+
+
+# ----------------------------------------------------------------------- RPSM
+RPSM_MAX_BINS = 4096
+
+
+class RpsmTree:
+    """The skeleton tree as the three host int arrays the RPSM entry points read
+    (include/posu.h): parent [J] (root = -1), child_ptr [J + 1], child_idx [J - 1]."""
+
+    def __init__(self, parents, children):
+        import numpy as np
+        self.parent = np.ascontiguousarray(parents, dtype=np.int32)
+        self.njoints = len(self.parent)
+        self.child_ptr = np.zeros(self.njoints + 1, dtype=np.int32)
+        self.child_ptr[1:] = np.cumsum([len(c) for c in children])
+        self.child_idx = np.ascontiguousarray([c for cs in children for c in cs] + [0], dtype=np.int32)
+        self.edges = [(j, c) for j, cs in enumerate(children) for c in cs]   # mask row e <-> edges[e]
+
+    def args(self):
+        return _host(self.parent), _host(self.child_ptr), _host(self.child_idx)
+
+    def by_child(self, values, what='limb_length'):
+        """dict keyed (parent, child) -> host f64 [J] indexed by the child joint; an array [J] is
+        taken as already in that form."""
+        import numpy as np
+        if not isinstance(values, dict):
+            out = np.ascontiguousarray(values, dtype=np.float64)
+            if out.shape != (self.njoints,):
+                raise ValueError('%s must be a dict keyed (parent, child) or [J] by child joint' % what)
+            return out
+        out = np.zeros(self.njoints, dtype=np.float64)
+        for p, c in self.edges:
+            if (p, c) not in values:
+                raise KeyError('%s has no entry for edge %r' % (what, (p, c)))
+            out[c] = float(values[(p, c)])
+        return out
+
+
+def _host(a):
+    import ctypes
+    return ctypes.c_void_p(a.ctypes.data)
+
+
+def _cube(nbins):
+    nbins = int(nbins)
+    return nbins, nbins * nbins * nbins
+
+
+def rpsm_grid(centers, size, nbins):
+    """compute_grid for a batch of boxes: centers [..., 3] f64 -> grid [..., nbins^3, 3] f64."""
+    require_cuda(centers)
+    nbins, n = _cube(nbins)
+    centers = centers.contiguous().double()
+    lead = tuple(centers.shape[:-1])
+    grid = torch.empty(lead + (n, 3), dtype=torch.float64, device=centers.device)
+    call('posu_rpsm_grid', ptr(centers), centers.numel() // 3, float(size), nbins, ptr(grid), stream_of(centers.device))
+    return grid
+
+
+def rpsm_unary(heatmaps, cams, affine, grid, image_size):
+    """heatmaps [G, V, J, H, W] f32, cams [G, V, 20] f64, affine [G, V, 2, 3] f64, grid [G, 1 | J, N, 3] f64,
+    image_size (w, h) -> unary [G, J, N] f64."""
+    require_cuda(heatmaps, cams, affine, grid)
+    g, v, j, h, w = heatmaps.shape
+    heatmaps = heatmaps.contiguous().float()
+    ng, n = grid.shape[1], grid.shape[2]
+    unary = torch.empty((g, j, n), dtype=torch.float64, device=heatmaps.device)
+    call('posu_rpsm_unary', ptr(heatmaps), ptr(cams.contiguous().double()), ptr(affine.contiguous().double()),
+         g, v, j, h, w, float(image_size[0]), float(image_size[1]), ptr(grid.contiguous().double()), ng, n,
+         ptr(unary), stream_of(heatmaps.device))
+    return unary
+
+
+def rpsm_infer(unary, tree, mask=None, grid=None, limb=None, tolerance=0.0, pose_grid=None):
+    """One grid level of max-product inference.  unary [G, J, N] f64; the pairwise term is either
+    mask [J - 1, ceil(N / 32), N] int32 (packed bits) or computed from grid [G, 1 | J, N, 3], limb (f64 [G, J]
+    on the device, by child joint, a row per group) and tolerance.  -> (bins [G, J] int32, pose [G, J, 3] f64 or None, energy [G, J, N],
+    maxv [G, J, N], state [G, J, N] int32).  pose needs a grid (pose_grid, default grid)."""
+    require_cuda(unary, mask, grid, pose_grid, limb)
+    unary = unary.contiguous().double()
+    g, j, n = unary.shape
+    dev = unary.device
+    energy, maxv = torch.empty_like(unary), torch.zeros_like(unary)
+    state = torch.zeros((g, j, n), dtype=torch.int32, device=dev)
+    if mask is not None:
+        mask = mask.contiguous()
+        if mask.dtype != torch.int32 or tuple(mask.shape) != (j - 1, (n + 31) // 32, n):
+            raise ValueError('mask must be int32 [J - 1, ceil(N / 32), N], got %s %s' % (mask.dtype, tuple(mask.shape)))
+    if grid is not None:
+        grid = grid.contiguous().double()
+    if limb is not None:
+        limb = _limb_table(limb, g, j)
+    call('posu_rpsm_infer', ptr(unary), *tree.args(), ptr(mask), ptr(grid), 1 if grid is None else grid.shape[1],
+         ptr(limb), float(tolerance), g, j, n, ptr(energy), ptr(maxv), ptr(state),
+         stream_of(dev))
+    pg = grid if pose_grid is None else pose_grid.contiguous().double()
+    bins = torch.empty((g, j), dtype=torch.int32, device=dev)
+    pose = None if pg is None else torch.empty((g, j, 3), dtype=torch.float64, device=dev)
+    pg_ptr, ngp = ptr(pg), (1 if pg is None else pg.shape[1])
+    call('posu_rpsm_backtrack', ptr(energy), ptr(state), *tree.args(), pg_ptr, ngp, g, j, n, ptr(bins), ptr(pose),
+         stream_of(dev))
+    return bins, pose, energy, maxv, state
+
+
+def _limb_table(limb, g, j):
+    limb = limb.contiguous().double()
+    if tuple(limb.shape) != (g, j):
+        raise ValueError('limb lengths must be [G, J] = [%d, %d] (a row per group, by child joint), got %s'
+                         % (g, j, tuple(limb.shape)))
+    return limb
+
+
+def rpsm_pairwise_mask(grid, tree, limb, thr, strict):
+    """grid [1 | J, N, 3] f64 -> packed constraint [J - 1, ceil(N / 32), N] int32 of every edge:
+    |norm(g_p[i] - g_c[j]) - limb[c]| < thr[c] (strict) or <= thr[c]; limb, thr host f64 [J] by child."""
+    require_cuda(grid)
+    grid = grid.contiguous().double()
+    ng, n = grid.shape[0], grid.shape[1]
+    mask = torch.empty((tree.njoints - 1, (n + 31) // 32, n), dtype=torch.int32, device=grid.device)
+    call('posu_rpsm_pairwise_mask', ptr(grid), ng, n, *tree.args(), tree.njoints, _host(limb), _host(thr),
+         int(bool(strict)), ptr(mask), stream_of(grid.device))
+    return mask
+
+
+def rpsm_run(heatmaps, cams, affine, image_size, grid_centers, grid_size, first_nbins, recur_nbins, recur_depth,
+             tolerance, limb, mask, tree, return_levels=False):
+    """The whole recursion for G groups in one enqueue (posu_rpsm_run) -> pose [G, J, 3] f64 (and, with
+    return_levels, [recur_depth + 1, G, J, 3]: the pose after level 1 and after every refinement).
+    limb: f64 [G, J] on the device, every group's limb lengths by child joint."""
+    require_cuda(heatmaps, cams, affine, grid_centers, mask, limb)
+    g, v, j, h, w = heatmaps.shape
+    dev = heatmaps.device
+    heatmaps = heatmaps.contiguous().float()
+    first_nbins, n1 = _cube(first_nbins)
+    recur_nbins, _ = _cube(recur_nbins)
+    mask = mask.contiguous()
+    if mask.dtype != torch.int32 or tuple(mask.shape) != (j - 1, (n1 + 31) // 32, n1):
+        raise ValueError('the level-1 constraint must be int32 [J - 1, ceil(N / 32), N] for N = %d bins, got %s %s'
+                         % (n1, mask.dtype, tuple(mask.shape)))
+    limb = _limb_table(limb, g, j)
+    nbytes = nat.load().posu_rpsm_workspace_bytes(g, j, first_nbins, recur_nbins)
+    work = torch.empty((max(int(nbytes), 0) + 8,), dtype=torch.uint8, device=dev)
+    pose = torch.empty((g, j, 3), dtype=torch.float64, device=dev)
+    levels = torch.empty((int(recur_depth) + 1, g, j, 3), dtype=torch.float64, device=dev) if return_levels else None
+    call('posu_rpsm_run', ptr(heatmaps), ptr(cams.contiguous().double()), ptr(affine.contiguous().double()), g, v, j,
+         h, w, float(image_size[0]), float(image_size[1]), ptr(grid_centers.contiguous().double()), float(grid_size),
+         first_nbins, recur_nbins, int(recur_depth), float(tolerance), ptr(limb), ptr(mask), *tree.args(),
+         ptr(work), int(nbytes), ptr(pose), ptr(levels), stream_of(dev))
+    return (pose, levels) if return_levels else pose
