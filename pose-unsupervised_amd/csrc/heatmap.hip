@@ -41,15 +41,22 @@ __global__ __launch_bounds__(64) void softargmax_fwd_kernel(const float* __restr
   const float* h = hm + static_cast<size_t>(map) * HW;
   float m = -INFINITY, s = 0.f, sx = 0.f, sy = 0.f;
   if ((HW & 3) == 0 && (W & 3) == 0) {
-    const float4* h4 = reinterpret_cast<const float4*>(h);
-    for (int i = lane; i < HW / 4; i += 64) {
-      const float4 v = h4[i];
+    auto four = [&](const float4 v, int i) {
       const int idx = i * 4;
       const int row = idx / W, col = idx - row * W;
       online_add(beta * v.x, col + 0.f, row, m, s, sx, sy);
       online_add(beta * v.y, col + 1.f, row, m, s, sx, sy);
       online_add(beta * v.z, col + 2.f, row, m, s, sx, sy);
       online_add(beta * v.w, col + 3.f, row, m, s, sx, sy);
+    };
+    // 16-B loads only from a 16-B aligned map; a view with a storage offset that is not a multiple of
+    // 4 floats reads the same four elements with 4-B loads, in the same order (the same bits out)
+    if ((reinterpret_cast<size_t>(h) & 15) == 0) {
+      const float4* h4 = reinterpret_cast<const float4*>(h);
+      for (int i = lane; i < HW / 4; i += 64) four(h4[i], i);
+    } else {
+      for (int i = lane; i < HW / 4; i += 64)
+        four(make_float4(h[4 * i], h[4 * i + 1], h[4 * i + 2], h[4 * i + 3]), i);
     }
   } else {
     for (int i = lane; i < HW; i += 64) {
@@ -108,16 +115,27 @@ __global__ __launch_bounds__(64) void softargmax_bwd_kernel(const float* __restr
     const float p = __expf(beta * hv - M) * inv_s;
     return beta * p * ((col - x) * gx + (row - y) * gy);
   };
-  // 16-B loads / stores (the same per-element arithmetic) when both maps are 16-B aligned: a view with
-  // a storage offset that is not a multiple of 4 floats takes the scalar loop
-  if ((HW & 3) == 0 && (W & 3) == 0 && ((reinterpret_cast<size_t>(h) | reinterpret_cast<size_t>(gh)) & 15) == 0) {
-    const float4* h4 = reinterpret_cast<const float4*>(h);
-    float4* g4 = reinterpret_cast<float4*>(gh);
-#pragma unroll 4
-    for (int i = lane; i < HW / 4; i += 64) {
-      const float4 v = h4[i];
+  if ((HW & 3) == 0 && (W & 3) == 0) {
+    auto four = [&](const float4 v, int i) {
       const int row = (i * 4) / W, col = i * 4 - row * W;
-      g4[i] = make_float4(one(v.x, row, col), one(v.y, row, col + 1), one(v.z, row, col + 2), one(v.w, row, col + 3));
+      return make_float4(one(v.x, row, col), one(v.y, row, col + 1), one(v.z, row, col + 2), one(v.w, row, col + 3));
+    };
+    // 16-B loads / stores when both maps are 16-B aligned; a view with a storage offset that is not a
+    // multiple of 4 floats moves the same four elements with 4-B accesses through the same arithmetic
+    // (the scalar loop below contracts its multiply-adds differently: not the same bits)
+    if (((reinterpret_cast<size_t>(h) | reinterpret_cast<size_t>(gh)) & 15) == 0) {
+      const float4* h4 = reinterpret_cast<const float4*>(h);
+      float4* g4 = reinterpret_cast<float4*>(gh);
+#pragma unroll 4
+      for (int i = lane; i < HW / 4; i += 64) g4[i] = four(h4[i], i);
+    } else {
+      for (int i = lane; i < HW / 4; i += 64) {
+        const float4 g = four(make_float4(h[4 * i], h[4 * i + 1], h[4 * i + 2], h[4 * i + 3]), i);
+        gh[4 * i] = g.x;
+        gh[4 * i + 1] = g.y;
+        gh[4 * i + 2] = g.z;
+        gh[4 * i + 3] = g.w;
+      }
     }
     return;
   }
@@ -238,14 +256,23 @@ __global__ __launch_bounds__(64) void mse_partial_kernel(const float* __restrict
   const float* t = gt + static_cast<size_t>(map) * HW;
   const float wt = w ? w[map] : 1.f;
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  if ((HW & 3) == 0 && ((reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(t)) & 15) == 0) {
+  if ((HW & 3) == 0) {
     const int n4 = HW >> 2;
-#pragma unroll 4
-    for (int j = lane; j < n4; j += 64) {
-      const float4 a = reinterpret_cast<const float4*>(p)[j], b = reinterpret_cast<const float4*>(t)[j];
+    auto four = [&](const float4 a, const float4 b, int j) {
       const float d0 = a.x * wt - b.x * wt, d1 = a.y * wt - b.y * wt, d2 = a.z * wt - b.z * wt,
                   d3 = a.w * wt - b.w * wt;
       acc[(j >> 6) & 3] += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    };
+    // 16-B loads when both maps are 16-B aligned; otherwise (a view with a storage offset that is not a
+    // multiple of 4 floats) the same four elements by 4-B loads, summed in the same association
+    if (((reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(t)) & 15) == 0) {
+#pragma unroll 4
+      for (int j = lane; j < n4; j += 64)
+        four(reinterpret_cast<const float4*>(p)[j], reinterpret_cast<const float4*>(t)[j], j);
+    } else {
+      for (int j = lane; j < n4; j += 64)
+        four(make_float4(p[4 * j], p[4 * j + 1], p[4 * j + 2], p[4 * j + 3]),
+             make_float4(t[4 * j], t[4 * j + 1], t[4 * j + 2], t[4 * j + 3]), j);
     }
   } else {
     for (int i = lane; i < HW; i += 64) {

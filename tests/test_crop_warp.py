@@ -84,6 +84,43 @@ def test_crop_warp_kernel_matches_the_oracle_bit_for_bit(cuda, out):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('out', ['u8', 'f32'])
+def test_crop_warp_kernel_non_square_output(cuda, out):
+    """image_size (w, h) = (48, 80): dw and dh in the pixel decode and in both output layouts."""
+    from posu import datapath
+    from utils.transforms import get_affine_transform
+    rng = np.random.default_rng(17)
+    sizes = [(37, 53), (5, 3), (64, 64)]
+    imgs = [_img(h, w, 20 + k) for k, (h, w) in enumerate(sizes)]
+    trans = np.stack([get_affine_transform(np.array([rng.uniform(0.2, 0.8) * w, rng.uniform(0.2, 0.8) * h]),
+                                           np.array([rng.uniform(0.05, 0.4)] * 2), rot, [48, 80])
+                      for (h, w), rot in zip(sizes, (0.0, 25.0, -40.0))])
+    got = datapath.crop_warp(imgs, trans, (48, 80), cuda, out=out).cpu().numpy()
+    assert got.shape == ((3, 80, 48, 3) if out == 'u8' else (3, 3, 80, 48))
+    for k, (im, M) in enumerate(zip(imgs, trans)):
+        ref = G.warp_affine_linear(im, M, (48, 80))
+        assert ref.any()
+        if out == 'u8':
+            np.testing.assert_array_equal(got[k], ref)
+        else:
+            np.testing.assert_array_equal(got[k], G.to_tensor_normalize(ref, datapath.IMAGENET_MEAN,
+                                                                        datapath.IMAGENET_STD))
+
+
+@pytest.mark.gpu
+def test_crop_warp_kernel_grid_stride(cuda):
+    """33 crops of 256 x 256 = 2,162,688 output pixels: above the 8192 blocks of 256 threads the launch
+    is capped at, so the stride loop takes a second trip.  The oracle is slow: three samples."""
+    from posu import datapath
+    rng = np.random.default_rng(19)
+    img = _img(300, 200, 30)
+    trans = np.stack([_getitem_trans(rng, 300, 200) for _ in range(33)])
+    got = datapath.crop_warp([img] * 33, trans, (256, 256), cuda, out='u8').cpu().numpy()
+    for k in (0, 16, 32):
+        np.testing.assert_array_equal(got[k], G.warp_affine_linear(img, trans[k], (256, 256)))
+
+
+@pytest.mark.gpu
 def test_crop_batch_is_getitem_crop(cuda):
     """crop_batch = get_affine_transform per sample + the warp: the network input __getitem__
     hands the model (ToTensor + Normalize)."""
