@@ -74,7 +74,9 @@ const char* posu_last_error(void);
  * Adam step (posu_adam_step); 16 (round 6) the split-fp16 dtype in the streamed Bottleneck tails
  * (posu_bottleneck_tail_stream_fwd / _next_fwd, layer1 / layer2 / layer3 at 256x256) and the
  * downsampling first-block tail (posu_bottleneck_down_tail_stream_fwd).  The RPSM entry points
- * (posu_rpsm_*) are additive to 16: new symbols only, the revision does not move.  The
+ * (posu_rpsm_*) and fp16 training's loss-scaling ones (posu_grad_stats, posu_grad_stats_workspace,
+ * posu_adam_step_dev, posu_loss_scale_update) are additive to 16: new symbols only, the revision
+ * does not move.  The
  * ctypes binding refuses a library of another revision. */
 int posu_abi_version(void);
 
@@ -639,6 +641,59 @@ typedef struct posu_adam_tensor {
 } posu_adam_tensor;
 int posu_adam_step(const posu_adam_tensor* tensors, int ntensors, double lr, double beta1, double beta2,
                    double eps, double weight_decay, long long step, void* stream);
+
+/* fp16 training (additive to ABI 16): loss scaling without a host synchronisation.  The three
+ * entry points below only enqueue on `stream`, allocate nothing and read whatever decides the
+ * step from device memory, so a training loop keeps its run-ahead and the calls can be captured
+ * in a hipGraph.  Tables are host memory, read during the call (the launches carry them).
+ *
+ * posu_grad_stats: one pass over a table of f32 gradient tensors.
+ *   found_inf (device float[1], required): zeroed by the call (hipMemsetAsync on the stream), then
+ *     1.0f if any element is inf or nan.
+ *   unscale != 0: g *= 1 / *scale in place (scale: device float[1], the loss scale; required then,
+ *     otherwise not read).
+ *   sumsq (device double[1], or NULL): the sum of squares of the gradients as the call leaves
+ *     them (after the in-place unscale, if any), squared and accumulated in double: per-block
+ *     partials in `workspace` (>= posu_grad_stats_workspace bytes, needed only with sumsq) summed
+ *     in a fixed order, the same bits on every run.
+ * posu_grad_stats_workspace: -1 for a null table or a negative size. */
+typedef struct posu_grad_tensor {
+  float* g;
+  long long n;
+} posu_grad_tensor;
+long long posu_grad_stats_workspace(const posu_grad_tensor* tensors, int ntensors);
+int posu_grad_stats(const posu_grad_tensor* tensors, int ntensors, const float* scale, int unscale,
+                    float* found_inf, double* sumsq, void* workspace, long long workspace_bytes,
+                    void* stream);
+
+/* posu_adam_step_dev: the update of posu_adam_step (same arithmetic) with the step count of every
+ * tensor in device memory (`step`, a float holding the number of steps taken; torch's
+ * capturable convention) and the bias corrections computed from it on the device, in double.
+ *   found_inf (device float[1], or NULL): when non-zero the call changes nothing: p, m, v and
+ *     step keep their bits.  Otherwise step += 1 first.
+ *   scale (device float[1], or NULL): the gradients are read as g / *scale.
+ *   sumsq (device double[1], or NULL) with max_norm > 0: the gradients are clipped to the global
+ *     norm max_norm, g * min(1, max_norm / (sqrt(*sumsq) / *scale + 1e-6)), where *sumsq is the
+ *     sum of squares of the gradients as stored (torch.nn.utils.clip_grad_norm_).  max_norm <= 0:
+ *     no clipping.
+ * With all three NULL this is a capturable plain Adam. */
+typedef struct posu_adam_dev_tensor {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  float* step;
+  long long n;
+} posu_adam_dev_tensor;
+int posu_adam_step_dev(const posu_adam_dev_tensor* tensors, int ntensors, double lr, double beta1, double beta2,
+                       double eps, double weight_decay, const float* found_inf, const float* scale,
+                       const double* sumsq, double max_norm, void* stream);
+
+/* posu_loss_scale_update: torch's _amp_update_scale_ on device scalars (one thread).  *found_inf
+ * != 0: *scale *= backoff, *growth_tracker = 0; else ++*growth_tracker, and when it reaches
+ * growth_interval (>= 1): *scale *= growth unless that is not finite, *growth_tracker = 0. */
+int posu_loss_scale_update(float* scale, int* growth_tracker, const float* found_inf, double growth,
+                           double backoff, int growth_interval, void* stream);
 
 /* Weight gradient dW[Cout][Creal][KH][KW] (f32, the nn.Conv2d weight layout) of a
  * conv over x[N,H,W,C] (C >= Creal, padded channels ignored) with output gradient

@@ -15,7 +15,8 @@ numerics -- heatmaps within 1e-3 of the reference, so an unchanged reference scr
 reference results), ``'bf16'`` (opt-in fast mode: bf16 operands / f32 accumulate,
 ~16x the fp32 MFMA rate; heatmaps deviate ~0.02 mean / 0.15 max from the fp32 path on
 R50@256) or ``'fp16'`` (IEEE fp16 operands / f32 accumulate, the fp16
-setting of BASELINE configs[4]).  Heatmaps are always returned as NCHW float32;
+setting of BASELINE configs[4]; it trains only with a ``posu.amp.LossScaler`` attached,
+``loss_scaler=`` / ``model.loss_scaler``).  Heatmaps are always returned as NCHW float32;
 ``layer1_out`` / ``deconv_out`` are returned as NCHW-shaped channels-last views of the
 NHWC activations in the compute dtype (zero-copy; fp32 in the default mode, like the
 reference's).
@@ -33,6 +34,7 @@ import torch
 import torch.nn as nn
 
 from posu import ops
+from posu.amp import LossScaler
 from posu.plan import PoseResNetPlan
 from posu.train_plan import TrainPlan, train_forward
 
@@ -81,7 +83,10 @@ _DECONV_CFG = {4: (1, 0), 3: (1, 1), 2: (0, 0)}  # kernel -> (padding, output_pa
 
 class PoseResNet(nn.Module):
 
-    def __init__(self, block, layers, cfg, precision='fp32', **kwargs):
+    # a posu.amp.LossScaler: what training in precision 'fp16' needs (train_plan)
+    loss_scaler = None
+
+    def __init__(self, block, layers, cfg, precision='fp32', loss_scaler=None, **kwargs):
         super(PoseResNet, self).__init__()
         extra = cfg.POSE_RESNET
         self.inplanes = 64
@@ -100,6 +105,7 @@ class PoseResNet(nn.Module):
         self.final_layer = nn.Conv2d(extra.NUM_DECONV_FILTERS[-1], cfg.NETWORK.NUM_JOINTS,
                                      kernel_size=k, stride=1, padding=1 if k == 3 else 0)
         self.precision = precision
+        self.loss_scaler = loss_scaler
         self._plan = None
         self._plan_key = None
         self._train_plan = None
@@ -148,7 +154,9 @@ class PoseResNet(nn.Module):
     def train_plan(self):
         """The training-mode launch sequence (posu.train_plan.TrainPlan); packs per step."""
         code = ops.dtype_code(self.precision)
-        if code in (ops.F16, ops.F16X3):
+        # fp16 activation gradients underflow without loss scaling: fp16 trains only with a LossScaler
+        # attached (the training loop scales the loss with it and steps through it)
+        if code == ops.F16X3 or (code == ops.F16 and not isinstance(self.loss_scaler, LossScaler)):
             raise NotImplementedError('training in fp16 / fp16x3 needs loss scaling; use precision bf16 or fp32')
         if self._train_plan is None or self._train_plan.code != code:
             self._train_plan = TrainPlan(self, code)
@@ -210,7 +218,7 @@ resnet_spec = {18: (BasicBlock, [2, 2, 2, 2]),
 def get_pose_net(cfg, is_train, **kwargs):
     """Reference factory (pose_resnet.py:257-267); extra kwarg ``precision`` = 'fp32' (default,
     reference numerics) | 'fp16x3' (split fp16: reference-parity numerics on the fp16 MFMAs) |
-    'bf16' | 'fp16' (opt-in fast modes)."""
+    'bf16' | 'fp16' (opt-in fast modes); ``loss_scaler`` = the posu.amp.LossScaler fp16 training needs."""
     block_class, layers = resnet_spec[cfg.POSE_RESNET.NUM_LAYERS]
     model = PoseResNet(block_class, layers, cfg, **kwargs)
     if is_train:

@@ -96,6 +96,11 @@ _SIGNATURES = {
     'posu_maxpool3x3s2_bwd_workspace': [_i, _i, _i, _i],
     'posu_maxpool3x3s2_bwd': [_i, _p, _i, _i, _i, _i, _p, _p, _p, _ll, _p],
     'posu_adam_step': [_p, _i, _d, _d, _d, _d, _d, _ll, _p],
+    # fp16 training: loss scaling on the device (additive to ABI 16)
+    'posu_grad_stats_workspace': [_p, _i],
+    'posu_grad_stats': [_p, _i, _p, _i, _p, _p, _p, _ll, _p],
+    'posu_adam_step_dev': [_p, _i, _d, _d, _d, _d, _d, _p, _p, _p, _d, _p],
+    'posu_loss_scale_update': [_p, _p, _p, _d, _d, _i, _p],
     # RPSM (additive to ABI 16)
     'posu_rpsm_workspace_bytes': [_i, _i, _i, _i],
     'posu_rpsm_grid': [_p, _i, _d, _i, _p, _p],
@@ -109,7 +114,8 @@ _SIGNATURES = {
 _RESTYPES = {'posu_last_error': ctypes.c_char_p, 'posu_conv2d_wgrad_workspace': ctypes.c_longlong,
              'posu_pack_job_blocks': ctypes.c_longlong,
              'posu_bn_workspace': ctypes.c_longlong, 'posu_maxpool3x3s2_bwd_workspace': ctypes.c_longlong,
-             'posu_stem_wgrad_workspace': ctypes.c_longlong, 'posu_rpsm_workspace_bytes': ctypes.c_longlong}
+             'posu_stem_wgrad_workspace': ctypes.c_longlong, 'posu_rpsm_workspace_bytes': ctypes.c_longlong,
+             'posu_grad_stats_workspace': ctypes.c_longlong}
 
 
 def library_path():

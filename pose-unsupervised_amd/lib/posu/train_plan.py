@@ -23,6 +23,12 @@ Parameters stay NCHW f32 in the nn.Modules (so optimizers, DDP and checkpoints a
 unchanged); they are packed into the kernels' layouts in the compute dtype once per
 step -- every weight of the network in ONE posu_pack_weights launch into buffers allocated
 once (packing.BatchedPacker) -- and their gradients come back f32 in the modules' layouts.
+
+The compute dtype is fp32, bf16 or fp16 (`code`; every kernel of the step has the three storage
+types).  In fp16 the loss is scaled by a posu.amp.LossScaler (PoseResNet.train_plan refuses fp16
+without one): the head's f32 heatmap gradient arrives already scaled and is converted to fp16
+once (backward_stage 4), an activation gradient that overflows fp16 becomes inf and reaches the
+f32 parameter gradients, where the scaler's statistics pass finds it and the step is skipped.
 """
 import torch
 
