@@ -47,6 +47,11 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert st == 1 and 'multiples of 32' in _native.last_error()
     st = lib.posu_conv2d_dgrad(_native.F16X3, p, 1, 8, 8, 64, p, 64, 3, 3, 1, 1, None, p, 8, 8, None)
     assert st == 1 and 'inference-only' in _native.last_error()
+    # the max-pool backward indexes its 2x2 input blocks in 32 bits: 2^36 of them (every int argument
+    # in range, the workspace size satisfied) are refused before any launch
+    for st in (lib.posu_maxpool3x3s2_bwd(_native.BF16, p, 32768, 1024, 1024, 64, p, p, p, 1 << 62, None),
+               lib.posu_maxpool3x3s2_bwd_idx(_native.BF16, p, p, 32768, 1024, 1024, 64, p, None)):
+        assert st == 1 and 'shape too large' in _native.last_error()
 
 
 def test_unknown_tiles_are_refused_without_a_gpu():

@@ -265,6 +265,106 @@ def test_bn_relu_bitmask_equals_the_y_masked_backward(cuda, code, c, nseg, size)
         assert torch.equal(a, b_)
 
 
+@pytest.mark.parametrize('nseg', [1, 2])
+@pytest.mark.parametrize('code', [F32, BF16])
+def test_bn_reductions_over_many_partial_blocks(cuda, code, nseg):
+    """128 x 128 pixels per segment at C = 64: 256 partial blocks per segment with one segment, 128 with
+    two, so the finalize sums them in four / two trips of 64 (the other tests stay within the first).
+    Statistics with running statistics, the mask-gated backward and the channel sum against float64
+    torch on the dtype-rounded inputs, at the BatchNorm test's tolerances for the dtype.  The
+    reference backward takes its ReLU mask from the y the forward stored (an element within rounding
+    of zero may sit on either side in float64)."""
+    g = torch.Generator().manual_seed(51)
+    c, h, w = 64, 128, 128
+    dt = ops.torch_dtype(code)
+    z = (torch.randn(nseg, c, h, w, generator=g) * 2 + 0.5).to(dt).double().requires_grad_(True)
+    gamma = (torch.rand(c, generator=g) + 0.5).double().requires_grad_(True)
+    beta = (torch.randn(c, generator=g) * 0.1).double().requires_grad_(True)
+    gy = torch.randn(nseg, c, h, w, generator=g).to(dt).double()
+    rm0, rv0 = torch.randn(c, generator=g) * 0.1, torch.rand(c, generator=g) + 0.5
+    rm, rv = rm0.double(), rv0.double()
+    bn = torch.cat([F.batch_norm(zs, rm, rv, gamma, beta, training=True, momentum=0.1, eps=1e-5)
+                    for zs in z.chunk(nseg)])
+    zd, gyd = _nhwc(z.detach(), cuda, dt), _nhwc(gy, cuda, dt)
+    gmd, btd = gamma.detach().float().to(cuda), beta.detach().float().to(cuda)
+    rmd, rvd = rm0.clone().to(cuda), rv0.clone().to(cuda)
+    mean, rstd, sc, sh = T.bn_train_fwd(zd, nseg, gmd, btd, 1e-5, 0.1, rmd, rvd)
+    yd, mask = T.bn_apply_mask(zd, nseg, sc, sh)
+    dz, _, dgam, dbet = T.bn_train_bwd(gyd, None, zd, nseg, mean, rstd, gmd, mask=mask)
+    csum = T.channel_sum(zd)
+    torch.cuda.synchronize()
+    zs = z.detach().view(nseg, 1, c, h, w)
+    mu_ref = zs.mean(dim=(1, 3, 4))
+    rstd_ref = 1 / torch.sqrt(zs.var(dim=(1, 3, 4), unbiased=False) + 1e-5)
+    grads = torch.autograd.grad(bn, [z, gamma, beta], gy * (_nchw(yd) > 0))
+    torch.testing.assert_close(csum.cpu().double(), z.detach().sum(dim=(0, 2, 3)), atol=1e-4, rtol=1e-5)
+    if code == F32:
+        tol = dict(atol=1e-4, rtol=1e-4)
+        torch.testing.assert_close(mean.cpu().double().view(nseg, c), mu_ref, **tol)
+        torch.testing.assert_close(rstd.cpu().double().view(nseg, c), rstd_ref, **tol)
+        torch.testing.assert_close(rmd.cpu().double(), rm, **tol)
+        torch.testing.assert_close(rvd.cpu().double(), rv, **tol)
+        torch.testing.assert_close(_nchw(yd).double(), F.relu(bn.detach()), **tol)
+        torch.testing.assert_close(_nchw(dz).double(), grads[0], atol=1e-4, rtol=1e-3)
+        torch.testing.assert_close(dgam.cpu().double(), grads[1], atol=1e-3, rtol=1e-4)
+        torch.testing.assert_close(dbet.cpu().double(), grads[2], atol=1e-3, rtol=1e-4)
+    else:
+        tol = dict(atol=1e-2, rtol=1e-2)
+        torch.testing.assert_close(mean.cpu().double().view(nseg, c), mu_ref, **tol)
+        torch.testing.assert_close(rstd.cpu().double().view(nseg, c), rstd_ref, **tol)
+        torch.testing.assert_close(rmd.cpu().double(), rm, **tol)
+        torch.testing.assert_close(rvd.cpu().double(), rv, **tol)
+        _close_lowp(_nchw(yd).double(), F.relu(bn.detach()))
+        _close_lowp(_nchw(dz).double(), grads[0], 0.03)
+        _close_lowp(dgam.cpu().double(), grads[1], 0.03)
+        _close_lowp(dbet.cpu().double(), grads[2], 0.03)
+
+
+def _off4(t):
+    """t's values in a contiguous view that starts 4 bytes into a larger buffer: per-channel
+    parameters that are not 16-byte aligned take the generic kernels."""
+    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+    buf[1:].copy_(t.reshape(-1))
+    v = buf[1:].view(t.shape)
+    assert v.data_ptr() % 16 == 4 and v.is_contiguous()
+    return v
+
+
+@pytest.mark.parametrize('code', [F32, BF16, F16])
+@pytest.mark.parametrize('c,nseg,size', [(256, 2, (3, 24, 20)), (64, 4, (2, 9, 7))])
+def test_bn_generic_kernels_equal_the_segment_major_ones(cuda, code, c, nseg, size):
+    """The apply and backward-apply passes have a segment-major kernel (per-channel parameters in
+    registers) and a generic one (parameters read per chunk; taken when a parameter row is not
+    16-byte aligned).  Both run the same arithmetic helpers: every output is equal bit for bit,
+    with a residual and ReLU, with the bit mask, and for each of the backward's three mask sources."""
+    g = torch.Generator().manual_seed(52)
+    b, h, w = size
+    dt = ops.torch_dtype(code)
+    z = _nhwc(torch.randn(nseg * b, c, h, w, generator=g) * 2 + 0.3, cuda, dt)
+    r = _nhwc(torch.randn(nseg * b, c, h, w, generator=g), cuda, dt)
+    gy = _nhwc(torch.randn(nseg * b, c, h, w, generator=g), cuda, dt)
+    gamma = (torch.rand(c, generator=g) + 0.5).to(cuda)
+    beta = (torch.randn(c, generator=g) * 0.1).to(cuda)
+    mean, rstd, sc, sh = T.bn_train_fwd(z, nseg, gamma, beta, 1e-5, 0.1)
+    assert all(t.data_ptr() % 16 == 0 for t in (mean, rstd, sc, sh))
+
+    def run(f):
+        m_, r_, sc_, sh_ = f(mean), f(rstd), f(sc), f(sh)
+        y = T.bn_apply(z, nseg, sc_, sh_, r, True)
+        y2, mask = T.bn_apply_mask(z, nseg, sc_, sh_, r)
+        outs = [y, y2, mask]
+        outs += T.bn_train_bwd(gy, y, z, nseg, m_, r_, gamma, want_gres=True)
+        outs += T.bn_train_bwd(gy, None, z, nseg, m_, r_, gamma, want_gres=True, mask=mask)
+        outs += T.bn_train_bwd(gy, None, z, nseg, m_, r_, gamma, want_gres=True, relu_from=(sc_, sh_))
+        return outs
+
+    seg, gen = run(lambda t: t), run(_off4)
+    torch.cuda.synchronize()
+    assert len(seg) == len(gen) == 15
+    for i, (a, b_) in enumerate(zip(seg, gen)):
+        assert torch.equal(a, b_), i
+
+
 @pytest.mark.parametrize('code', [F32, BF16])
 @pytest.mark.parametrize('shape', [(4, 17, 16, 64), (2, 32, 30, 64), (2, 9, 9, 128)])
 def test_fused_stem_bn_relu_maxpool_equals_the_two_pass_path(cuda, code, shape):
