@@ -776,6 +776,72 @@ int posu_stem_wgrad_views(int dtype, const float* const* views, int nviews, int 
                           const void* dz, float* dw, void* workspace, long long workspace_bytes,
                           void* stream);
 
+/* ------------------------------------------------- heatmap mutual-information loss */
+/* HeatmapMILoss over HeatmapDiscriminator (lib/core/loss.py:636-781, lib/models/discriminator.py
+ * :225-242; called per view from lib/core/function.py:259-278).  Additive to ABI 16.  The reference
+ * builds all Q x Q (feature row, heatmap value) pairs of an image as a dense [N Q Q, C + 1] tensor
+ * (loss.py:705-713) and runs Linear(C + 1 -> cm, no bias) -> BatchNorm1d -> LeakyReLU(0.2) ->
+ * Linear(cm -> cm / 4) -> BatchNorm1d -> LeakyReLU(0.2) -> Linear(cm / 4 -> 1) over it.  Here the
+ * first Linear splits into A[n, i, :] + h[n, j] w_h with A = F_s W_f^T (W1 = [w_h | W_f]) and every
+ * pass over the pairs recomputes the rest from A and h; nothing per pair is stored but the score.
+ *
+ *   feat:  channels-last features [S N, H, W, C] of `dtype` (POSU_F32 / POSU_BF16 / POSU_F16);
+ *   hm:    heatmaps [S N, J, H, W] f32, of which joint `joint_idx` is used;
+ *   idx:   DEVICE int32 [S N, Q], sampled positions in [0, H W); idx_host: NULL, or a host copy,
+ *          which is then checked (an index outside the map is refused).  Without a host copy the
+ *          range is the caller's contract; the kernels clamp a stray index into the map;
+ *   S segments (the reference's views) of N images: BatchNorm statistics per segment over its
+ *          N Q^2 rows, like posu_bn_train_fwd's nseg;
+ *   params: HOST array of 13 device pointers, read during the call: W1 [cm, C + 1], gamma1, beta1,
+ *          running_mean1, running_var1 [cm], W2 [cm / 4, cm], b2, gamma2, beta2, running_mean2,
+ *          running_var2 [cm / 4], w3 [cm / 4], b3 [1]  (the running statistics may be NULL when
+ *          training != 0; they are never written);
+ *   training != 0: batch statistics; stats [S, 3, cm + cm / 4] f32 out = per segment the batch
+ *          mean, the biased and the unbiased variance of BN1's cm then BN2's cm / 4 channels (the
+ *          caller updates its running buffers from them, segment by segment);
+ *          training == 0: the running statistics, one pass, stats not written (may be NULL);
+ *   u:     [S N, Q, Q] f32 out, u[n, i, j] = the score of (feature row idx[n, i], heatmap value
+ *          idx[n, j]): the reference's row order.
+ * Limits (POSU_ERR_ARG before any launch): cm in {32, 64, 128}; C a multiple of 8, at most 512;
+ * Q <= 256; joint_idx in [0, J); S N Q^2 cm < 2^31; non-null required pointers.
+ * workspace: >= posu_heatmap_mi_workspace(S, N, Q, cm) bytes, 16-byte aligned: S N Q (cm + 2) + S N Q^2
+ * floats (A, h, dh and one scalar per pair), up to 2 S N Q^2 more for the backward's dA buffers (one
+ * per j slab, as many slabs as fit), plus what does not grow with the pairs (derived per-segment
+ * values and the f64 partials of the reductions: *reduction_bytes, optional out).  No activation
+ * 16 or 64 wide is stored per pair. */
+long long posu_heatmap_mi_workspace(int S, int N, int Q, int cm, long long* reduction_bytes);
+int posu_heatmap_pair_scores_fwd(int dtype, const void* feat, const float* hm, int S, int N, int H, int W,
+                                 int C, int J, int joint_idx, const int* idx, const int* idx_host, int Q,
+                                 int cm, const float* const* params, int training, float eps, float* stats,
+                                 float* u, void* workspace, long long workspace_bytes, void* stream);
+/* Its backward (the autograd of loss.py:770-773 through the discriminator) from du [S N, Q, Q],
+ * recomputing the forward from the same inputs (stats: scratch of the forward's size when
+ * training != 0).  Three optional outputs, NULL = not computed:
+ *   dparams: f32 [posu_heatmap_dparams_floats(C, cm)] = dW1 [cm (C + 1)] | dgamma1 | dbeta1 [cm] |
+ *            dW2 [cm / 4 * cm] | db2 | dgamma2 | dbeta2 | dw3 [cm / 4] | db3 [1];
+ *   dfeat:   [S N, H, W, C] of `dtype`, zero outside the sampled positions;
+ *   dhm:     [S N, J, H, W] f32, zero outside joint_idx and the sampled positions.
+ * A position sampled more than once receives the sum over its occurrences, added in index order.
+ * No floating-point atomics: two calls on the same inputs give the same bits. */
+long long posu_heatmap_dparams_floats(int C, int cm);
+int posu_heatmap_pair_scores_bwd(int dtype, const void* feat, const float* hm, int S, int N, int H, int W,
+                                 int C, int J, int joint_idx, const int* idx, const int* idx_host, int Q,
+                                 int cm, const float* const* params, int training, float eps, float* stats,
+                                 const float* du, float* dparams, void* dfeat, float* dhm, void* workspace,
+                                 long long workspace_bytes, void* stream);
+/* The mutual-information measures on u [S N, Q, Q] (loss.py:719-757), one loss per segment:
+ *   measure 0, JSD (get_jsd_loss): mean over the off-diagonal of softplus(-u) + u - log 2 minus
+ *     the mean over the diagonal of log 2 - softplus(-u)  (Q >= 2);
+ *   measure 1, NCE (get_infonce_loss): per (n, i) -log_softmax of [u_ii, u_i0 .. u_i,Q-1 with -10
+ *     at j = i] at position 0, averaged.
+ * loss: [S] f32; workspace >= posu_pair_mi_workspace(S) bytes.  Backward: du [S N, Q, Q] from
+ * gloss [S] (device). */
+long long posu_pair_mi_workspace(int S);
+int posu_pair_mi_loss_fwd(const float* u, int S, int N, int Q, int measure, float* loss, void* workspace,
+                          long long workspace_bytes, void* stream);
+int posu_pair_mi_loss_bwd(const float* u, int S, int N, int Q, int measure, const float* gloss, float* du,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,16 @@
   are read from ``<DATASET.ROOT>/testdata/fundamental_matrix.pkl`` like the reference
   ({(subject, i, j): 3x3}), or given directly as a dict.
 
-The MI / InfoNCE / JSD discriminator losses of the reference are outside this build.
+* HeatmapMILoss (loss.py:636-781): the mutual information (JSD or InfoNCE) between the
+  sampled heatmap values of one joint and the backbone's low-level feature rows, scored by
+  HeatmapDiscriminator over all Q x Q pairs per image.  The reference materialises the pairs as
+  a [N Q Q, C + 1] tensor; here the pair scores, their backward and the measures are kernels
+  that never form it (csrc/heatmap_mi.hip), and ``views`` runs the reference's per-view calls
+  (function.py:266-267 / 276-277) as one call with per-view BatchNorm statistics.
+
+The reference's other discriminator losses -- MILoss (its gradient penalty needs a double
+backward through the kernels), ViewMILoss, JointsMILoss and the domain loss -- are outside this
+build and raise if asked for.
 """
 import itertools
 import os
@@ -83,3 +92,101 @@ class FundamentalLoss:
         if self.use_target_weight:
             w = torch.stack([t.reshape(batch_size, -1) for t in target_weight], dim=0)
         return ops.epipolar_loss(x, w, self.F, self.subject_indices(subject))
+
+
+def _not_built(name, why):
+    def ctor(*args, **kwargs):
+        raise NotImplementedError('%s is not part of this build: %s' % (name, why))
+    ctor.__name__ = name
+    return ctor
+
+
+MILoss = _not_built('MILoss', 'its gradient penalty needs a double backward through the kernels')
+ViewMILoss = _not_built('ViewMILoss', 'only HeatmapMILoss is built')
+JointsMILoss = _not_built('JointsMILoss', 'only HeatmapMILoss is built')
+
+
+class HeatmapMILoss:
+    """Reference lib/core/loss.py:636-781.  Constructor and ``__call__`` are the reference's (one
+    view in, the scalar loss out); ``sample_indices`` exposes the position sampling, ``indices=``
+    takes positions drawn elsewhere, and ``views`` sums the loss over a list of views in one call."""
+
+    MAP = 64   # the reference asserts 64 x 64 low-level and heatmap maps (loss.py:686, 714-716)
+
+    def __init__(self, cfg, discriminator_dict):
+        self.use_target_weight = cfg.LOSS.USE_TARGET_WEIGHT
+        self.measure = cfg.LOSS.HEATMAP_MI_MEASURE
+        if self.measure not in ops.MI_MEASURES:
+            raise NotImplementedError('LOSS.HEATMAP_MI_MEASURE %r (JSD and NCE are built)' % (self.measure,))
+        self.sigma = cfg.NETWORK.SIGMA
+        # image px per heatmap px, (w, h)
+        self.feat = torch.as_tensor(np.asarray(cfg.NETWORK.IMAGE_SIZE, dtype=np.float64)
+                                    / np.asarray(cfg.NETWORK.HEATMAP_SIZE, dtype=np.float64))
+        self.heatmap_d = discriminator_dict['heatmap_discriminator']
+
+    # -- sampling (host-side torch, as in the reference: loss.py:646-672, 691-703)
+    def window(self, loc):
+        """The (2r + 1)^2 linear positions around `loc` [N], r = 3 sigma + 2, clamped to the map
+        (the linear index is clamped, like the reference's, so a window at the border repeats
+        positions): [N, P]."""
+        r = int(self.sigma * 3 + 2)
+        off = torch.arange(-r, r + 1)
+        grid = (off[:, None] * self.MAP + off[None, :]).reshape(-1)
+        return (loc.reshape(-1, 1).long() + grid[None, :]).clamp(0, self.MAP * self.MAP - 1)
+
+    def locations(self, meta, joint_idx, generator=None):
+        """Per image the window centre: the ground-truth joint (joints_2d_transformed / feat + 0.5,
+        truncated, clamped to the map) when it is visible, a uniformly random position otherwise.
+        Image n keeps slot n (the reference moves the invisible joints' random draws to the end of
+        the batch, loss.py:697-699; which image a random centre lands on does not matter to it)."""
+        m = self.MAP
+        j2d = torch.as_tensor(meta['joints_2d_transformed']).double().cpu()
+        gt = (j2d / self.feat + 0.5).long().clamp(0, m - 1)
+        gt = (gt[:, :, 1] * m + gt[:, :, 0])[:, joint_idx]
+        vis = torch.as_tensor(meta['joints_vis']).cpu()[:, joint_idx, 0] != 0
+        rnd = torch.randint(0, m * m, gt.shape, generator=generator)
+        return torch.where(vis, gt, rnd)
+
+    def sample_indices(self, meta, joint_idx, generator=None, return_locations=False):
+        """[N, P // 2 + P // 4] positions: half of the window's P entries without replacement, then a
+        quarter as many distinct positions from outside the window."""
+        m = self.MAP
+        loc = self.locations(meta, joint_idx, generator)
+        win = self.window(loc)
+        n, p = win.shape
+        pick = torch.rand(n, p, generator=generator).argsort(dim=1)[:, :p // 2]
+        inside = win.gather(1, pick)
+        score = torch.rand(n, m * m, generator=generator)
+        score.scatter_(1, win, -1.0)
+        outside = score.topk(p // 4, dim=1).indices
+        idx = torch.cat([inside, outside], dim=1)
+        return (idx, loc) if return_locations else idx
+
+    def _check_maps(self, low_features, high_features):
+        if tuple(low_features.shape[2:]) != (self.MAP, self.MAP) or tuple(high_features.shape[2:]) != (self.MAP,
+                                                                                                      self.MAP):
+            raise NotImplementedError('HeatmapMILoss takes 64 x 64 maps (like the reference), got low %s, high %s'
+                                      % (tuple(low_features.shape[2:]), tuple(high_features.shape[2:])))
+
+    def __call__(self, low_features, high_features, target_weight, meta, joint_idx, indices=None):
+        """low_features [N, C, 64, 64], high_features [N, J, 64, 64] (cuda), meta on the host."""
+        self._check_maps(low_features, high_features)
+        if indices is None:
+            indices = self.sample_indices(meta, joint_idx)
+        u = self.heatmap_d.pair_scores(low_features, high_features, indices, joint_idx, nseg=1)
+        return ops.pair_mi_loss(u, self.measure, 1)[0]
+
+    def views(self, low_list, out_list, weight_list, meta_list, joint_idx, indices=None):
+        """sum over views of __call__ (function.py:266-267 / 276-277) as one call: the views are
+        the segments of the kernels, each with its own BatchNorm statistics, and the running
+        buffers end as after the per-view calls in order.  indices: None or one [N, Q] per view."""
+        nseg = len(low_list)
+        for l, o in zip(low_list, out_list):
+            self._check_maps(l, o)
+        if indices is None:
+            indices = [self.sample_indices(m, joint_idx) for m in meta_list]
+        low = low_list[0] if nseg == 1 else torch.cat(list(low_list), dim=0)
+        out = out_list[0] if nseg == 1 else torch.cat(list(out_list), dim=0)
+        idx = torch.cat([torch.as_tensor(i).cpu() for i in indices], dim=0)
+        u = self.heatmap_d.pair_scores(low, out, idx, joint_idx, nseg=nseg)
+        return ops.pair_mi_loss(u, self.measure, nseg).sum()

@@ -110,12 +110,23 @@ _SIGNATURES = {
     'posu_rpsm_pairwise_mask': [_p, _i, _i, _p, _p, _p, _i, _p, _p, _i, _p, _p],
     'posu_rpsm_run': [_p, _p, _p, _i, _i, _i, _i, _i, _d, _d, _p, _d, _i, _i, _i, _d, _p, _p, _p, _p, _p, _p, _ll,
                       _p, _p, _p],
+    # heatmap mutual-information loss (additive to ABI 16)
+    'posu_heatmap_mi_workspace': [_i, _i, _i, _i, _p],
+    'posu_heatmap_dparams_floats': [_i, _i],
+    'posu_heatmap_pair_scores_fwd': [_i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _i, _i, _p, _i, _f, _p, _p, _p,
+                                     _ll, _p],
+    'posu_heatmap_pair_scores_bwd': [_i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _i, _i, _p, _i, _f, _p, _p, _p,
+                                     _p, _p, _p, _ll, _p],
+    'posu_pair_mi_workspace': [_i],
+    'posu_pair_mi_loss_fwd': [_p, _i, _i, _i, _i, _p, _p, _ll, _p],
+    'posu_pair_mi_loss_bwd': [_p, _i, _i, _i, _i, _p, _p, _p],
 }
 _RESTYPES = {'posu_last_error': ctypes.c_char_p, 'posu_conv2d_wgrad_workspace': ctypes.c_longlong,
              'posu_pack_job_blocks': ctypes.c_longlong,
              'posu_bn_workspace': ctypes.c_longlong, 'posu_maxpool3x3s2_bwd_workspace': ctypes.c_longlong,
              'posu_stem_wgrad_workspace': ctypes.c_longlong, 'posu_rpsm_workspace_bytes': ctypes.c_longlong,
-             'posu_grad_stats_workspace': ctypes.c_longlong}
+             'posu_grad_stats_workspace': ctypes.c_longlong, 'posu_heatmap_mi_workspace': ctypes.c_longlong,
+             'posu_heatmap_dparams_floats': ctypes.c_longlong, 'posu_pair_mi_workspace': ctypes.c_longlong}
 
 
 def library_path():

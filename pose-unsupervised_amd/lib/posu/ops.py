@@ -3,8 +3,10 @@
 Every function here takes/returns torch tensors on a cuda (HIP) device, launches on
 PyTorch's current stream, and raises if given CPU tensors: there is no fallback
 path.  Autograd Functions wrap the kernels that the training step differentiates
-through (soft-argmax, crop affine, epipolar loss, heatmap MSE).
+through (soft-argmax, crop affine, epipolar loss, heatmap MSE, the heatmap
+mutual-information pair scores and measures).
 """
+import numpy as np
 import torch
 
 from . import _native as nat
@@ -685,3 +687,176 @@ def rpsm_run(heatmaps, cams, affine, image_size, grid_centers, grid_size, first_
          first_nbins, recur_nbins, int(recur_depth), float(tolerance), ptr(limb), ptr(mask), *tree.args(),
          ptr(work), int(nbytes), ptr(pose), ptr(levels), stream_of(dev))
     return (pose, levels) if return_levels else pose
+
+
+# ------------------------------------------------------- heatmap mutual-information loss
+MI_MEASURES = {'JSD': 0, 'NCE': 1}
+# order of the parameter table of posu_heatmap_pair_scores_* (include/posu.h)
+_MI_PARAMS = ('W1', 'g1', 'be1', 'rm1', 'rv1', 'W2', 'b2', 'g2', 'be2', 'rm2', 'rv2', 'w3', 'b3')
+_MI_GRADS = ('W1', 'g1', 'be1', 'W2', 'b2', 'g2', 'be2', 'w3', 'b3')   # dparams order
+
+
+def heatmap_mi_workspace(nseg, n, q, cm):
+    """(bytes, bytes of it that do not grow with the pairs) of the pair-score workspace."""
+    import ctypes
+    red = ctypes.c_longlong(0)
+    total = nat.load().posu_heatmap_mi_workspace(nseg, n, q, cm, ctypes.byref(red))
+    if total < 0:
+        raise ValueError('heatmap MI: unsupported shape S=%d N=%d Q=%d c_m=%d' % (nseg, n, q, cm))
+    return int(total), int(red.value)
+
+
+def _mi_param_table(p, training):
+    import ctypes
+    tab = (ctypes.c_void_p * len(_MI_PARAMS))()
+    for k, name in enumerate(_MI_PARAMS):
+        t = p[name]
+        if t is None:
+            if not (training and name in ('rm1', 'rv1', 'rm2', 'rv2')):
+                raise ValueError('heatmap MI: parameter %s is missing' % name)
+            tab[k] = None
+        else:
+            tab[k] = t.data_ptr()
+    return tab
+
+
+def _mi_geometry(feat, hm, idx, p):
+    b, h, w, c = feat.shape
+    q = idx.shape[1]
+    cm = p['W1'].shape[0]
+    if hm.shape[0] != b or tuple(hm.shape[2:]) != (h, w) or idx.shape[0] != b:
+        raise ValueError('heatmap MI: features %s, heatmaps %s and indices %s disagree'
+                         % (tuple(feat.shape), tuple(hm.shape), tuple(idx.shape)))
+    if p['W1'].shape[1] != c + 1:
+        raise ValueError('heatmap MI: the discriminator takes %d inputs, the features have %d channels (+ 1)'
+                         % (p['W1'].shape[1], c))
+    return b, h, w, c, hm.shape[1], q, cm
+
+
+class _HeatmapPairScores(torch.autograd.Function):
+    """u[n, i, j] of the discriminator over (feature row idx[n, i], heatmap value idx[n, j]).
+    feat: [B, H, W, C] contiguous (f32 / bf16 / f16); hm: [B, J, H, W] f32; idx: [B, Q] int32 on the
+    device, idx_host its host copy (checked by the library).  Returns (u, stats)."""
+
+    @staticmethod
+    def forward(ctx, feat, hm, idx, idx_host, joint_idx, nseg, training, eps, *params):
+        p = dict(zip(_MI_PARAMS, params))
+        b, h, w, c, j, q, cm = _mi_geometry(feat, hm, idx, p)
+        n = b // nseg
+        ws_bytes, _ = heatmap_mi_workspace(nseg, n, q, cm)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=feat.device)
+        k2 = cm // 4
+        stats = torch.empty((nseg, 3, cm + k2), dtype=torch.float32, device=feat.device)
+        u = torch.empty((b, q, q), dtype=torch.float32, device=feat.device)
+        tab = _mi_param_table(p, training)
+        call('posu_heatmap_pair_scores_fwd', nat.dtype_code_of(feat), ptr(feat), ptr(hm), nseg, n, h, w, c, j,
+             int(joint_idx), ptr(idx), idx_host.ctypes.data, q, cm, tab, int(training), float(eps), ptr(stats), ptr(u),
+             ptr(ws), ws_bytes, stream_of(feat.device))
+        # training mode normalises with batch statistics: the running buffers (updated in place by
+        # the module after this call) are not part of the backward
+        saved = [None if (training and name in ('rm1', 'rv1', 'rm2', 'rv2')) else p[name] for name in _MI_PARAMS]
+        ctx.save_for_backward(feat, hm, idx, *[t for t in saved if t is not None])
+        ctx.saved_names = [name for name, t in zip(_MI_PARAMS, saved) if t is not None]
+        ctx.idx_host, ctx.joint_idx, ctx.nseg, ctx.training, ctx.eps = idx_host, int(joint_idx), nseg, training, eps
+        ctx.mark_non_differentiable(stats)
+        return u, stats
+
+    @staticmethod
+    def backward(ctx, du, _dstats):
+        feat, hm, idx = ctx.saved_tensors[:3]
+        p = dict.fromkeys(_MI_PARAMS)
+        p.update(zip(ctx.saved_names, ctx.saved_tensors[3:]))
+        b, h, w, c, j, q, cm = _mi_geometry(feat, hm, idx, p)
+        nseg, n, k2 = ctx.nseg, b // ctx.nseg, cm // 4
+        need = ctx.needs_input_grad
+        want_feat, want_hm = need[0], need[1]
+        grad_pos = {name: 8 + _MI_PARAMS.index(name) for name in _MI_GRADS}
+        want_params = any(need[k] for k in grad_pos.values())
+        out = [None] * (8 + len(_MI_PARAMS))
+        if not (want_feat or want_hm or want_params):
+            return tuple(out)
+        dev = feat.device
+        ws_bytes, _ = heatmap_mi_workspace(nseg, n, q, cm)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        stats = torch.empty((nseg, 3, cm + k2), dtype=torch.float32, device=dev)
+        dparams = torch.empty(nat.load().posu_heatmap_dparams_floats(c, cm), dtype=torch.float32,
+                              device=dev) if want_params else None
+        dfeat = torch.empty_like(feat) if want_feat else None
+        dhm = torch.empty_like(hm) if want_hm else None
+        du = du.contiguous().float()
+        tab = _mi_param_table(p, ctx.training)
+        call('posu_heatmap_pair_scores_bwd', nat.dtype_code_of(feat), ptr(feat), ptr(hm), nseg, n, h, w, c, j,
+             ctx.joint_idx, ptr(idx), ctx.idx_host.ctypes.data, q, cm, tab, int(ctx.training), float(ctx.eps),
+             ptr(stats), ptr(du), ptr(dparams), ptr(dfeat), ptr(dhm), ptr(ws), ws_bytes, stream_of(dev))
+        out[0], out[1] = dfeat, dhm
+        if want_params:
+            sizes = {'W1': cm * (c + 1), 'g1': cm, 'be1': cm, 'W2': k2 * cm, 'b2': k2, 'g2': k2, 'be2': k2, 'w3': k2,
+                     'b3': 1}
+            off = 0
+            for name in _MI_GRADS:
+                if need[grad_pos[name]]:
+                    out[grad_pos[name]] = dparams[off:off + sizes[name]].view(p[name].shape)
+                off += sizes[name]
+        return tuple(out)
+
+
+def heatmap_pair_scores(low_features, heatmaps, indices, joint_idx, params, nseg=1, training=True, eps=1e-5):
+    """Scores u [B, Q, Q] of the heatmap discriminator over every (feature row, heatmap value) pair
+    of each image (reference core/loss.py:674-717 + models/discriminator.py:225-242), and the batch
+    statistics [nseg, 3, c_m + c_m // 4] (mean, biased, unbiased variance) of the two BatchNorms.
+
+    low_features [B, C, H, W] (f32 / bf16 / f16): a tensor whose channel stride is 1 (the backbone's
+    x1.permute(0, 3, 1, 2)) is read in place, anything else is made channels-last once.
+    heatmaps [B, J, H, W]; indices [B, Q] integer (host or device); B = nseg * N, statistics per
+    segment.  params: dict of W1, g1, be1, rm1, rv1, W2, b2, g2, be2, rm2, rv2, w3, b3 (f32)."""
+    require_cuda(low_features, heatmaps, *[t for t in params.values() if t is not None])
+    if low_features.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        low_features = low_features.float()
+    feat = low_features.permute(0, 2, 3, 1)
+    if not feat.is_contiguous():
+        feat = feat.contiguous()
+    if feat.shape[0] % nseg:
+        raise ValueError('heatmap MI: %d images do not split into %d segments' % (feat.shape[0], nseg))
+    hm = heatmaps.contiguous().float()
+    idx_host = np.ascontiguousarray(indices.detach().cpu().numpy().astype(np.int32))
+    idx = torch.from_numpy(idx_host).to(feat.device)
+    plist = []
+    for name in _MI_PARAMS:
+        t = params[name]
+        plist.append(None if t is None else t.contiguous().float())
+    return _HeatmapPairScores.apply(feat, hm, idx, idx_host, joint_idx, nseg, bool(training), eps, *plist)
+
+
+class _PairMILoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, measure, nseg):
+        b, q, _ = u.shape
+        ws_bytes = nat.load().posu_pair_mi_workspace(nseg)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=u.device)
+        loss = torch.empty((nseg,), dtype=torch.float32, device=u.device)
+        call('posu_pair_mi_loss_fwd', ptr(u), nseg, b // nseg, q, measure, ptr(loss), ptr(ws), ws_bytes,
+             stream_of(u.device))
+        ctx.save_for_backward(u)
+        ctx.measure, ctx.nseg = measure, nseg
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        u, = ctx.saved_tensors
+        b, q, _ = u.shape
+        gloss = gloss.contiguous().float()
+        du = torch.empty_like(u)
+        call('posu_pair_mi_loss_bwd', ptr(u), ctx.nseg, b // ctx.nseg, q, ctx.measure, ptr(gloss), ptr(du),
+             stream_of(u.device))
+        return du, None, None
+
+
+def pair_mi_loss(u, measure, nseg=1):
+    """The mutual-information measure ('JSD' or 'NCE', reference core/loss.py:719-757) on pair scores
+    u [nseg * N, Q, Q]: one loss per segment, [nseg]."""
+    require_cuda(u)
+    if measure not in MI_MEASURES:
+        raise NotImplementedError('heatmap MI measure %r (JSD and NCE are built)' % (measure,))
+    if u.dim() != 3 or u.shape[1] != u.shape[2] or u.shape[0] % nseg:
+        raise ValueError('pair_mi_loss: u must be [nseg * N, Q, Q], got %s' % (tuple(u.shape),))
+    return _PairMILoss.apply(u.contiguous().float(), MI_MEASURES[measure], nseg)

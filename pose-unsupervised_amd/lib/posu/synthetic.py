@@ -241,3 +241,50 @@ def fundamental_dict(distortion=True):
         for i, j in itertools.permutations(range(4), 2):
             out[(s, i, j)] = fundamental(cams[i], cams[j]).astype(np.float32)
     return out
+
+
+# ------------------------------------------------------------ heatmap mutual-information loss
+def heatmap_mi_cfg(sigma=2, channels=256, inter_channels=64, measure='JSD', joint_idx=0, image_size=256,
+                   num_joints=16):
+    """The config fields HeatmapMILoss / HeatmapDiscriminator read (reference experiments/mixed/
+    resnet50/pseudo_label/256_fund5_heatmap_*.yaml: JSD, INTER_CHANNELS 64, 64 x 64 maps)."""
+    return _ns(
+        NETWORK=_ns(NUM_JOINTS=num_joints, SIGMA=sigma, IMAGE_SIZE=np.array([image_size] * 2),
+                    HEATMAP_SIZE=np.array([64, 64])),
+        LOSS=_ns(USE_TARGET_WEIGHT=True, USE_HEATMAP_MI_LOSS=True, HEATMAP_MI_MEASURE=measure,
+                 HEATMAP_MI_LOSS_WEIGHT=0.1),
+        HEATMAP_DISCRIMINATOR=_ns(INPUT_CHANNELS=channels + 1, INTER_CHANNELS=inter_channels, JOINT_IDX=joint_idx),
+    )
+
+
+def heatmap_mi_case(seed, n, channels, inter_channels, joint_idx=0, num_joints=16, corners=False, image_size=256):
+    """Seeded inputs of one HeatmapMILoss call as float64 numpy arrays: low-level features
+    [n, channels, 64, 64], heatmaps [n, J, 64, 64], the meta fields the sampling reads, and the
+    discriminator's state (reference names) with non-trivial BatchNorm weights and running
+    statistics.  corners: joint `joint_idx` of image 0 sits at (0, 0), of image 1 at the far
+    corner, and is invisible in image 2 (windows clamped at the border repeat positions)."""
+    rng = _rng('heatmap_mi', seed)
+    c_in, cm, k2 = channels + 1, inter_channels, inter_channels // 4
+    case = {
+        'low_features': rng.standard_normal((n, channels, 64, 64)),
+        'heatmaps': rng.random((n, num_joints, 64, 64)),
+        'joints_2d_transformed': rng.uniform(8.0, image_size - 8.0, (n, num_joints, 2)),
+        'joints_vis': np.ones((n, num_joints, 3)),
+    }
+    if corners:
+        case['joints_2d_transformed'][0, joint_idx] = (0.0, 0.0)
+        case['joints_2d_transformed'][1, joint_idx] = (image_size - 1.0, image_size - 1.0)
+        case['joints_vis'][2, joint_idx] = 0.0
+    state = {}
+    for name, width, fan in (('0', cm, c_in), ('3', k2, cm), ('6', 1, k2)):
+        state['block_nonlinear.%s.weight' % name] = rng.standard_normal((width, fan)) / np.sqrt(fan)
+        if name != '0':
+            state['block_nonlinear.%s.bias' % name] = 0.1 * rng.standard_normal(width)
+    for name, width in (('1', cm), ('4', k2)):
+        state['block_nonlinear.%s.weight' % name] = rng.uniform(0.5, 1.5, width)
+        state['block_nonlinear.%s.bias' % name] = 0.2 * rng.standard_normal(width)
+        state['block_nonlinear.%s.running_mean' % name] = 0.3 * rng.standard_normal(width)
+        state['block_nonlinear.%s.running_var' % name] = rng.uniform(0.5, 2.0, width)
+        state['block_nonlinear.%s.num_batches_tracked' % name] = np.array(3, dtype=np.int64)
+    case['state'] = state
+    return case
