@@ -76,7 +76,8 @@ const char* posu_last_error(void);
  * downsampling first-block tail (posu_bottleneck_down_tail_stream_fwd).  The RPSM entry points
  * (posu_rpsm_*) and fp16 training's loss-scaling ones (posu_grad_stats, posu_grad_stats_workspace,
  * posu_adam_step_dev, posu_loss_scale_update) are additive to 16: new symbols only, the revision
- * does not move.  The
+ * does not move; so are the heatmap mutual-information ones and the training loop's metrics
+ * (posu_pck_accuracy, posu_grad_row_norms, posu_meters_update and their workspace queries).  The
  * ctypes binding refuses a library of another revision. */
 int posu_abi_version(void);
 
@@ -841,6 +842,49 @@ int posu_pair_mi_loss_fwd(const float* u, int S, int N, int Q, int measure, floa
                           long long workspace_bytes, void* stream);
 int posu_pair_mi_loss_bwd(const float* u, int S, int N, int Q, int measure, const float* gloss, float* du,
                           void* stream);
+
+/* ------------------------------------------------- training-loop metrics */
+/* What lib/core/function.py:91-527 (train) computes about a step besides the losses, without a
+ * read-back.  Additive to ABI 16.  Stream-ordered, no allocation, no atomics, f64 partials in a
+ * fixed order: two calls on the same inputs give the same bits.
+ *
+ * PCK accuracy of V (1..8) views (accuracy, lib/core/evaluate.py:42-73, with calc_dists / dist_acc
+ * :17-39 over get_max_preds, lib/core/inference.py:19-47; called per view on host copies at
+ * function.py:463-466).  outputs / targets: HOST arrays of V device pointers to [N, J, H, W] f32
+ * (any 4-byte alignment; 16-byte aligned maps are read with 16-byte loads).  Per map pair the
+ * argmaxes are posu_argmax2d_fwd's at post_process = 0 (first maximum, (0, 0) when maxval <= 0);
+ * then in f64 valid = tx > 1 && ty > 1, d = sqrt((px / (H/10) - tx / (H/10))^2 + (py / (W/10) -
+ * ty / (W/10))^2) -- x over H and y over W is the reference's pairing -- and hit = valid && d < thr.
+ *   acc  [V, J + 1] f64: acc[j + 1] = hits / valid over n, -1 without a valid target; acc[0] = avg;
+ *   avg  [V] f64: the accuracies >= 0 added joint by joint in index order / cnt (0 when cnt == 0);
+ *   cnt  [V] int32: joints with a valid target;
+ *   pred [V, N, J, 2] f32: the outputs' argmax coordinates;
+ *   step [2] f64: the means over the views of avg and of cnt, added as np.mean adds them
+ *        (function.py:467-468);
+ *   workspace >= posu_pck_accuracy_workspace(V, N, J) bytes (-1: V outside 1..8, a non-positive
+ *        size, or 2^31 map pairs and more). */
+long long posu_pck_accuracy_workspace(int V, int N, int J);
+int posu_pck_accuracy(const float* const* outputs, const float* const* targets, int V, int N, int J, int H,
+                      int W, double thr, double* acc, double* avg, int* cnt, float* pred, double* step,
+                      void* workspace, long long workspace_bytes, void* stream);
+
+/* The gradient-norm watch (check_grad_norm, lib/utils/gradients.py:31-39; function.py:352-362).
+ * grads: HOST array of V (1..8) device pointers to [N, L] f32, NULL = a view without a gradient
+ * (skipped).  Per row the p-norm (p = 1 or 2) accumulated in f64;
+ *   out[0] = sum over the views of (sum of row norms / number of rows whose norm != 0), f64
+ * (a view whose rows are all zero adds 0 / 0 = NaN, as the reference's does; 0 when every pointer
+ * is NULL).  workspace >= posu_grad_row_norms_workspace(V, N) bytes, 8-byte aligned. */
+long long posu_grad_row_norms_workspace(int V, int N);
+int posu_grad_row_norms(const float* const* grads, int V, int N, long long L, int p, double* out,
+                        void* workspace, long long workspace_bytes, void* stream);
+
+/* AverageMeter.update (function.py:693-709) for every meter of the loop in one launch.
+ * table [M, 3] f64 device (val, sum, count), M <= 64; v, w [M] f64 device; active [M] u8 HOST mask,
+ * read during the call (it becomes a launch argument, so a captured launch keeps it).  Per active
+ * slot m: val = v[m]; sum += v[m] * w[m]; count += w[m], each operation rounded on its own like
+ * the host's float arithmetic; avg = sum / count is left to the reader. */
+int posu_meters_update(double* table, int M, const double* v, const double* w, const unsigned char* active,
+                       void* stream);
 
 #ifdef __cplusplus
 }

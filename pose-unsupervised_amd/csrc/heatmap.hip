@@ -9,6 +9,7 @@
 //   soft-argmax bwd : dh = beta p ((col-x) gx + (row-y) gy)
 //   argmax          : get_max_preds + get_final_preds post-process + transform_preds
 //                     (lib/core/inference.py:19-75)
+#include "argmax_map.h"
 #include "posu_common.h"
 
 namespace posu {
@@ -153,32 +154,12 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ h
   if (map >= NJ) return;
   const int HW = H * W;
   const float* h = hm + static_cast<size_t>(map) * HW;
-  float best = -INFINITY;
-  int bidx = 0x7fffffff;
-  for (int i = lane; i < HW; i += 64) {
-    const float v = h[i];
-    if (v > best) {  // strict: the first (smallest) index of a tie within the lane
-      best = v;
-      bidx = i;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bidx, o, 64);
-    if (ov > best || (ov == best && oi < bidx)) {
-      best = ov;
-      bidx = oi;
-    }
-  }
+  float best;
+  int bidx;
+  wave_argmax<false>(h, HW, lane, best, bidx);  // argmax_map.h: the 4-B loop, as before
   if (lane == 0) {
-    if (bidx == 0x7fffffff) bidx = 0;  // all -inf / NaN map
-    float px = static_cast<float>(bidx % W);
-    float py = floorf(static_cast<float>(bidx) / W);
-    if (!(best > 0.f)) {
-      px = 0.f;
-      py = 0.f;
-    }
+    float px, py;
+    argmax_coords(best, bidx, W, px, py);
     if (post) {
       const int ix = static_cast<int>(floorf(px + 0.5f)), iy = static_cast<int>(floorf(py + 0.5f));
       if (1 < ix && ix < W - 1 && 1 < iy && iy < H - 1) {

@@ -4,6 +4,9 @@ The argmax of output and target heatmaps runs on the HIP argmax kernel
 (core.inference.get_max_preds); the per-joint distance / threshold arithmetic on the
 [N, J] coordinates is the reference's, on the host, with the same return values:
 (acc [J+1], avg_acc, cnt, pred).
+
+``accuracy_device`` is the training loop's form: every view in one call, argmaxes and the PCK
+arithmetic in one kernel chain (posu_pck_accuracy), results left on the device.
 """
 import numpy as np
 
@@ -54,3 +57,15 @@ def accuracy(output, target, hm_type='gaussian', thr=0.5):
         avg_acc = avg_acc / cnt
         acc[0] = avg_acc
     return acc, avg_acc, cnt, pred
+
+
+def accuracy_device(output_list, target_list, thr=0.5):
+    """``accuracy`` for a list of views in one call that stays on the device (the training loop's
+    per-view calls on host copies, function.py:463-468): V x [N, J, h, w] f32 cuda outputs and targets
+    -> (acc [V, J+1] f64, avg [V] f64, cnt [V] int32, pred [V, N, J, 2] f32, step [2] f64), cuda
+    tensors; row v is what ``accuracy(output_list[v], target_list[v])`` returns and step is
+    (np.mean(avg), np.mean(cnt)).  Nothing is read back.  ``thr`` is applied (hit = d < thr), as in this
+    module's ``accuracy``; the reference's ``accuracy`` takes a ``thr`` but never hands it to ``dist_acc``,
+    so there every call counts at 0.5."""
+    from posu import ops
+    return ops.pck_accuracy(list(output_list), list(target_list), thr)

@@ -20,10 +20,18 @@ pseudo-label targets times LOSS.MSE_LOSS_WEIGHT.
 (keys heatmaps / locations / joint_names_order, u2a-selected joints) and
 ``dataset.evaluate``'s perf indicator.  Debug-image dumps and tensorboard are not part
 of this build.
+
+``train`` keeps the reference signature (function.py:91-92) and runs its step for the losses this
+build has.  What the reference's loop reads back every step -- ``loss.item()`` and one ``.item()`` per
+loss, ``accuracy`` on host copies of every view's heatmaps, the gradient-norm watch, the boolean-mask
+selection of the H36M samples -- stays on the device here (posu_pck_accuracy, posu_grad_row_norms,
+posu_meters_update; the selection is decided on the host from ``meta``), so between two log lines
+the host only enqueues.
 """
 import logging
 import os
 import time
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -56,6 +64,325 @@ def select_out_h36m(raw_features, aggre_features, meta):
         raw_h36m.append(r[idx])
         agg_h36m.append(a[idx])
     return raw_h36m, agg_h36m
+
+
+def _h36m_rows(m):
+    return [i for i, s in enumerate(m['source']) if s == 'h36m']
+
+
+def _take_rows(t, rows):
+    """Rows of a host meta entry (tensor, array or list)."""
+    if isinstance(t, torch.Tensor):
+        return t[torch.as_tensor(rows, dtype=torch.long)]
+    if isinstance(t, np.ndarray):
+        return t[np.asarray(rows, dtype=np.int64)]
+    return [t[i] for i in rows]
+
+
+def select_out_h36m_meta(meta, key_list):
+    """function.py:62-75: per view the `key_list` entries of the H36M samples (host data, selected on
+    the host); [] when the batch has none."""
+    new_meta = []
+    for m in meta:
+        rows = _h36m_rows(m)
+        if not rows:
+            break
+        new_meta.append({key: _take_rows(m[key], rows) for key in key_list})
+    assert len(new_meta) == 0 or len(new_meta) == len(meta)
+    return new_meta
+
+
+def percent_of_datasource(meta):
+    """function.py:78-88: the share of each data source in the batch, for the log line."""
+    sources = list(meta[0]['source'])
+    counts = {}
+    for s in sources:
+        counts[s] = counts.get(s, 0) + 1
+    return ''.join('{} {:.1%}\t'.format(k, v / len(sources)) for k, v in counts.items())
+
+
+class AverageMeter(object):
+    """Computes and stores the average and current value (function.py:693-709), on the host; train()
+    keeps its per-step meters in a device table (posu_meters_update) and fills these only to print."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.val = 0
+        self.avg = 0
+        self.sum = 0
+        self.count = 0
+
+    def update(self, val, n=1):
+        self.val = val
+        self.sum += val * n
+        self.count += n
+        self.avg = self.sum / self.count
+
+
+# losses of the reference's loop that this build does not have (core.loss raises when one is built)
+UNBUILT_LOSS_FLAGS = ('USE_GLOBAL_MI_LOSS', 'USE_LOCAL_MI_LOSS', 'USE_DOMAIN_TRANSFER_LOSS', 'USE_VIEW_MI_LOSS',
+                      'USE_JOINTS_MI_LOSS')
+# slots of train()'s device meter table
+METERS = ('loss', 'mse', 'acc', 'consistent', 'fund', 'hmi_g', 'hmi_d', 'mse_grad', 'fund_grad', 'hmi_grad')
+
+
+def _loss_scaler_of(model):
+    """The posu.amp.LossScaler an fp16 base model carries (DDP-wrapped or not, multi-view or not)."""
+    base = getattr(model, 'module', model)
+    for m in (base, getattr(base, 'resnet', None)):
+        scaler = getattr(m, 'loss_scaler', None)
+        if scaler is not None:
+            return scaler
+    return None
+
+
+class _DeviceMeters:
+    """The loop's AverageMeters as one [M, 3] f64 device table (val, sum, count), updated by one
+    posu_meters_update launch per step and read only to print."""
+
+    def __init__(self, device):
+        self.device = device
+        self.table = torch.zeros((len(METERS), 3), dtype=torch.float64, device=device)
+        self.vals = torch.zeros((len(METERS),), dtype=torch.float64, device=device)
+        self._weights = {}
+        self._slots = {}
+
+    def weights(self, nsamples):
+        """The reference's weights (function.py:376-457): len(input) * N for the loss and MSE meters
+        and, at function.py:380, for the consistent meter as well; 1 for the others; the accuracy slot
+        is filled per step with the device value cnt."""
+        if nsamples not in self._weights:
+            w = [float(nsamples) if name in ('loss', 'mse', 'consistent') else 1.0 for name in METERS]
+            self._weights[nsamples] = torch.tensor(w, dtype=torch.float64).to(self.device)
+        return self._weights[nsamples]
+
+    def _slot_index(self, slots):
+        if slots not in self._slots:
+            self._slots[slots] = torch.tensor(slots, dtype=torch.long).to(self.device)
+        return self._slots[slots]
+
+    def update(self, values, nsamples, acc_weight):
+        """values: {meter name: 0-dim device tensor or Python number}; the others keep their state.
+        The f32 scalars (the losses) and the f64 ones (accuracy, gradient norms) each reach the value
+        vector as one stack and one index_copy_; then one posu_meters_update launch."""
+        groups = {torch.float32: ([], []), torch.float64: ([], []), 'host': ([], [])}
+        for slot, name in enumerate(METERS):
+            v = values.get(name)
+            if v is None:
+                continue
+            key = v.dtype if isinstance(v, torch.Tensor) else 'host'
+            if key not in groups:
+                v, key = v.double(), torch.float64
+            groups[key][0].append(slot)
+            groups[key][1].append(v.detach().reshape(()) if key != 'host' else float(v))
+        for key, (slots, vs) in groups.items():
+            if not slots:
+                continue
+            if key == 'host':   # a term that was skipped this step (no H36M sample): its Python 0
+                stacked = torch.tensor(vs, dtype=torch.float64).to(self.device)
+            else:
+                stacked = torch.stack(vs).to(torch.float64)
+            self.vals.index_copy_(0, self._slot_index(tuple(slots)), stacked)
+        w = self.weights(nsamples)
+        if acc_weight is not None:
+            acc = METERS.index('acc')
+            w[acc:acc + 1].copy_(acc_weight.reshape(1))
+        ops.meters_update(self.table, self.vals, w, [name in values for name in METERS])
+
+    def read(self):
+        """One device-to-host copy -> {name: AverageMeter}."""
+        host = self.table.cpu().numpy()
+        out = {}
+        for name, (val, total, count) in zip(METERS, host):
+            m = AverageMeter()
+            m.val, m.sum, m.count = float(val), float(total), float(count)
+            m.avg = m.sum / m.count if m.count else 0
+            out[name] = m
+        return out
+
+
+def train(config, data, model_dict, criterion_dict, optim_dict, epoch, output_dir, writer_dict, rank):
+    """function.py:91-527 for the losses of this build: weighted MSE on the raw (and, with AGGRE, the
+    routed) outputs, the consistent loss, FundamentalLoss, HeatmapMILoss (discriminator steps on even
+    epochs, the generator term on odd ones) and the gradient-norm watch, then the optimiser step (through
+    the base model's posu.amp.LossScaler when it has one).  PCK accuracy, the watch and the running meters
+    stay on the device: on a step with i % PRINT_FREQ != 0 nothing is read back and nothing synchronises.
+    Returns {meter name: {'val', 'avg', 'sum', 'count'}} read once after the last step (rank 0; {} on
+    the other ranks).  Debug images are not written."""
+    from core.evaluate import accuracy_device
+    from utils.gradients import check_grad_norm
+    from utils.transforms import generate_integral_preds_2d_th, transform_back_th
+    L = config.LOSS
+    for flag in UNBUILT_LOSS_FLAGS:
+        if getattr(L, flag, False):
+            raise NotImplementedError('train: LOSS.%s is set, and that loss is not part of this build' % flag)
+    device = torch.device('cuda', rank)
+    is_aggre = bool(config.NETWORK.AGGRE)
+    fuse = is_aggre and bool(getattr(config.TEST, 'FUSE_OUTPUT', False))
+    use_cons = bool(getattr(L, 'USE_CONSISTENT_LOSS', False))
+    use_fund = bool(getattr(L, 'USE_FUNDAMENTAL_LOSS', False))
+    use_hmi = bool(getattr(L, 'USE_HEATMAP_MI_LOSS', False))
+    watch = bool(getattr(L, 'WATCH_GRAD_NORM', False))
+    hmi_generator = use_hmi and epoch % 2 != 0
+    mse_crit = criterion_dict['mse_weights']
+    base_model = model_dict['base_model']
+    base_opt = optim_dict['base_model']
+    scaler = _loss_scaler_of(base_model)
+    batch_time, data_time = AverageMeter(), AverageMeter()
+    meters = _DeviceMeters(device) if rank == 0 else None
+
+    for model in model_dict.values():
+        model.train()
+
+    end = time.time()
+    for i, (input, target, weight, meta) in enumerate(data):
+        data_time.update(time.time() - end)
+        input = [view.to(device, non_blocking=False) for view in input]
+        nsamples = len(input) * input[0].size(0)
+        raw_features, aggre_features, low_features, high_features = base_model(input)
+        output = fuse_routing(raw_features, aggre_features, is_aggre, meta) if fuse else raw_features
+
+        step_vals = {}
+        loss = 0
+        mse_loss = 0
+        target_cuda = [t.to(device, non_blocking=False) for t in target]
+        weight_cuda = [w.to(device, non_blocking=False) for w in weight]
+        for t, w, r in zip(target_cuda, weight_cuda, raw_features):
+            mse_loss = mse_loss + mse_crit(r, t, w) * L.MSE_LOSS_WEIGHT
+        loss = loss + mse_loss
+        if is_aggre:   # function.py:185-188, as written there: mse_loss is added to the loss again
+            for t, w, o in zip(target_cuda, weight_cuda, output):
+                mse_loss = mse_loss + mse_crit(o, t, w) * L.MSE_LOSS_WEIGHT
+            loss = loss + mse_loss
+
+        if use_hmi:    # function.py:259-278
+            joint_idx = config.HEATMAP_DISCRIMINATOR.JOINT_IDX
+            if not hmi_generator:
+                hmi_loss_d = criterion_dict['heatmap_mi'].views([l.detach() for l in low_features],
+                                                                [o.detach() for o in output], weight_cuda, meta,
+                                                                joint_idx=joint_idx)
+                optim_dict['heatmap_discriminator'].zero_grad()
+                hmi_loss_d.backward()
+                optim_dict['heatmap_discriminator'].step()
+                step_vals['hmi_d'] = hmi_loss_d
+            else:
+                hmi_loss_g = criterion_dict['heatmap_mi'].views(low_features, output, weight_cuda, meta,
+                                                                joint_idx=joint_idx) * L.HEATMAP_MI_LOSS_WEIGHT
+                loss = loss + hmi_loss_g
+                step_vals['hmi_g'] = hmi_loss_g
+
+        # the H36M samples, chosen on the host from meta (no boolean-mask indexing: that is a nonzero
+        # and a synchronisation); every view selects by its own meta, like select_out_h36m
+        consistent_loss = 0
+        fund_loss = 0
+        rows = [_h36m_rows(m) for m in meta]
+        have_h36m = len(rows[0]) != 0
+        if (use_fund or (is_aggre and use_cons)) and have_h36m:
+            # one index upload per view and step; None: every sample of the view is H36M
+            index = [None if len(r) == len(m['source']) else torch.tensor(r, dtype=torch.long).to(device)
+                     for r, m in zip(rows, meta)]
+
+            def pick(tensors):
+                return [t if k is None else t.index_select(0, k) for t, k in zip(tensors, index)]
+            s_raw = pick(raw_features)
+            s_weight, s_output = pick(weight_cuda), pick(output)
+            s_meta = select_out_h36m_meta(meta, ['center', 'scale', 'subject'])
+            assert len(s_weight[0]) == len(s_output[0]) == len(s_raw[0])
+            if is_aggre and use_cons:   # function.py:291-296
+                cal_loss = criterion_dict['mse'](torch.cat(s_raw, dim=0), torch.cat(pick(aggre_features), dim=0))
+                loss = loss + cal_loss * L.CONSISTENT_LOSS_WEIGHT
+                consistent_loss = cal_loss.detach().double() * L.CONSISTENT_LOSS_WEIGHT
+            if use_fund:                # function.py:299-310
+                joints2d_list = transform_back_th(config, [generate_integral_preds_2d_th(o) for o in s_output],
+                                                  s_meta)
+                fund_loss = criterion_dict['fundamental'](joints2d_list, s_weight, s_meta) * L.FUNDAMENTAL_LOSS_WEIGHT
+                loss = loss + fund_loss
+
+        if watch and have_h36m:         # function.py:352-362
+            losses_dict = OrderedDict([('mse', mse_loss)])
+            if use_fund:
+                losses_dict['fund'] = fund_loss
+            if hmi_generator:
+                losses_dict['hmi_g'] = hmi_loss_g
+            grad_dict = check_grad_norm(losses_dict, raw_features, norm=1)
+            for name, value in grad_dict.items():
+                step_vals[{'mse': 'mse_grad', 'fund': 'fund_grad', 'hmi_g': 'hmi_grad'}[name]] = value
+
+        base_opt.zero_grad()
+        if scaler is not None:
+            scaler.scale(loss).backward()
+            scaler.step(base_opt)
+            scaler.update()
+        else:
+            loss.backward()
+            base_opt.step()
+
+        if rank == 0:
+            step_vals['loss'] = loss
+            step_vals['mse'] = mse_loss
+            if use_cons:
+                step_vals['consistent'] = consistent_loss
+            if use_fund:
+                step_vals['fund'] = fund_loss
+            _, _, _, _, acc_step = accuracy_device(output, target_cuda)
+            step_vals['acc'] = acc_step[0]
+            meters.update(step_vals, nsamples, acc_step[1])
+            batch_time.update(time.time() - end)
+            end = time.time()
+
+            if i % config.PRINT_FREQ == 0:
+                m = meters.read()       # the one read between two log lines
+                msg = 'Epoch: [{0}][{1}/{2}]\t' \
+                      'Time {batch_time.val:.3f}s ({batch_time.avg:.3f}s)\t' \
+                      'Speed {speed:.1f} samples/s\t' \
+                      'Data {data_time.val:.3f}s ({data_time.avg:.3f}s)\t' \
+                      'Memory {memory:.1f}\t' \
+                      'Loss {loss.val:.5f} ({loss.avg:.5f})\t' \
+                      'MSE Loss {mse_loss.val:.4f} ({mse_loss.avg:.4f})\t' \
+                      'Accuracy {acc.val:.3f} ({acc.avg:.3f})\t'.format(
+                          epoch, i, len(data), batch_time=batch_time, speed=nsamples / batch_time.val,
+                          data_time=data_time, loss=m['loss'], acc=m['acc'],
+                          memory=torch.cuda.memory_allocated(0), mse_loss=m['mse'])
+                if use_cons:
+                    msg += 'Consistent Loss {cons_loss.val:.5f} ({cons_loss.avg:.5f})\t'.format(cons_loss=m['consistent'])
+                if use_fund:
+                    msg += 'Fundamental Loss {fund_loss.val:.4f} ({fund_loss.avg:.4f})\t'.format(fund_loss=m['fund'])
+                if use_hmi:
+                    msg += 'Hmi_g Loss {hmi_loss_g.val:.4f} ({hmi_loss_g.avg:.4f})\t' \
+                           'Hmi_d Loss {hmi_loss_d.val:.4f} ({hmi_loss_d.avg:.4f})\t'.format(
+                               hmi_loss_g=m['hmi_g'], hmi_loss_d=m['hmi_d'])
+                if watch:
+                    msg += 'MSE_grad Norm {mse_grad_norm.val:.6f} ({mse_grad_norm.avg:.6f})\t'.format(
+                        mse_grad_norm=m['mse_grad'])
+                    if use_fund:
+                        msg += 'Fund_grad Norm {fund_grad_norm.val:.4f} ({fund_grad_norm.avg:.4f})\t'.format(
+                            fund_grad_norm=m['fund_grad'])
+                    if hmi_generator:
+                        msg += 'Hmi_grad Norm {hmi_grad_norm.val:.5f} ({hmi_grad_norm.avg:.5f})\t'.format(
+                            hmi_grad_norm=m['hmi_grad'])
+                msg += percent_of_datasource(meta)
+                logger.info(msg)
+
+                if writer_dict is not None:
+                    writer = writer_dict['writer']
+                    global_steps = writer_dict['train_global_steps']
+                    writer.add_scalar('train_loss', m['loss'].val, global_steps)
+                    writer.add_scalar('train_mse_loss', m['mse'].val, global_steps)
+                    writer.add_scalar('train_acc', m['acc'].val, global_steps)
+                    writer_dict['train_global_steps'] = global_steps + 1
+                    if use_cons:
+                        writer.add_scalar('train_consistent_loss', m['consistent'].val, global_steps)
+                    if use_fund:
+                        writer.add_scalar('train_fundamental_loss', m['fund'].val, global_steps)
+                    if use_hmi:
+                        writer.add_scalar('train_hmi_loss_d', m['hmi_d'].val, global_steps)
+                        writer.add_scalar('train_hmi_loss_g', m['hmi_g'].val, global_steps)
+
+    if meters is None:
+        return {}
+    return {name: {'val': m.val, 'avg': m.avg, 'sum': m.sum, 'count': m.count} for name, m in meters.read().items()}
 
 
 def _run_model(model, views, hflip):

@@ -2,6 +2,8 @@
 
 * JointsMSELoss (loss.py:64-86): weighted per-joint heatmap MSE, one fused
   reduction kernel + its backward.
+* MeanMSELoss: nn.MSELoss(reduction='mean') on the same kernels, differentiable in both arguments
+  (what the training loop's consistent loss needs: both of its inputs carry gradients).
 * FundamentalLoss (loss.py:89-133): epipolar residual |x_j^T F_{s,i,j} x_i| over the
   V(V-1) ordered view pairs, one kernel for the whole batch (the reference issues
   B x 12 small matmuls from a Python loop) + its backward.  The fundamental matrices
@@ -37,6 +39,15 @@ class JointsMSELoss(torch.nn.Module):
     def forward(self, output, target, target_weight):
         w = target_weight if self.use_target_weight else None
         return ops.joints_mse(output, target, w)
+
+
+class MeanMSELoss(torch.nn.Module):
+    """torch.nn.MSELoss(reduction='mean') of two [N, J, ...] f32 cuda tensors on the JointsMSE kernels, with
+    a gradient for both arguments: a drop-in for the ``criterion_dict['mse']`` that the training loop's
+    consistent loss calls (function.py:294)."""
+
+    def forward(self, input, target):
+        return ops.mse_mean(input, target)
 
 
 class FundamentalLoss:

@@ -120,13 +120,20 @@ _SIGNATURES = {
     'posu_pair_mi_workspace': [_i],
     'posu_pair_mi_loss_fwd': [_p, _i, _i, _i, _i, _p, _p, _ll, _p],
     'posu_pair_mi_loss_bwd': [_p, _i, _i, _i, _i, _p, _p, _p],
+    # training-loop metrics (additive to ABI 16)
+    'posu_pck_accuracy_workspace': [_i, _i, _i],
+    'posu_pck_accuracy': [_p, _p, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p, _p, _p, _ll, _p],
+    'posu_grad_row_norms_workspace': [_i, _i],
+    'posu_grad_row_norms': [_p, _i, _i, _ll, _i, _p, _p, _ll, _p],
+    'posu_meters_update': [_p, _i, _p, _p, _p, _p],
 }
 _RESTYPES = {'posu_last_error': ctypes.c_char_p, 'posu_conv2d_wgrad_workspace': ctypes.c_longlong,
              'posu_pack_job_blocks': ctypes.c_longlong,
              'posu_bn_workspace': ctypes.c_longlong, 'posu_maxpool3x3s2_bwd_workspace': ctypes.c_longlong,
              'posu_stem_wgrad_workspace': ctypes.c_longlong, 'posu_rpsm_workspace_bytes': ctypes.c_longlong,
              'posu_grad_stats_workspace': ctypes.c_longlong, 'posu_heatmap_mi_workspace': ctypes.c_longlong,
-             'posu_heatmap_dparams_floats': ctypes.c_longlong, 'posu_pair_mi_workspace': ctypes.c_longlong}
+             'posu_heatmap_dparams_floats': ctypes.c_longlong, 'posu_pair_mi_workspace': ctypes.c_longlong,
+             'posu_pck_accuracy_workspace': ctypes.c_longlong, 'posu_grad_row_norms_workspace': ctypes.c_longlong}
 
 
 def library_path():

@@ -484,6 +484,42 @@ def joints_mse(pred, gt, w=None):
     return _JointsMSE.apply(pred, gt, w)
 
 
+class _MSEMean(torch.autograd.Function):
+    """mean((a - b)^2) with a gradient for both arguments (the JointsMSE kernels, unweighted: a sum of
+    per-joint means / J; d/db = -d/da)."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        n, j = a.shape[:2]
+        hw = a[0, 0].numel()
+        a = a.contiguous().float()
+        b = b.contiguous().float()
+        ws = torch.empty((n * j,), dtype=torch.float32, device=a.device)
+        loss = torch.empty((), dtype=torch.float32, device=a.device)
+        call('posu_joints_mse_fwd', ptr(a), ptr(b), None, n, j, hw, ptr(ws), ptr(loss), stream_of(a.device))
+        ctx.save_for_backward(a, b)
+        return loss / j
+
+    @staticmethod
+    def backward(ctx, gloss):
+        a, b = ctx.saved_tensors
+        n, j = a.shape[:2]
+        hw = a[0, 0].numel()
+        gloss = (gloss.contiguous().float() / j).reshape(1)
+        ga = torch.empty_like(a)
+        call('posu_joints_mse_bwd', ptr(a), ptr(b), None, n, j, hw, ptr(gloss), ptr(ga), stream_of(a.device))
+        return (ga if ctx.needs_input_grad[0] else None), (-ga if ctx.needs_input_grad[1] else None)
+
+
+def mse_mean(a, b):
+    """torch.nn.MSELoss(reduction='mean') of two [N, J, ...] f32 cuda tensors on the JointsMSE kernels,
+    differentiable in both (the training loop's consistent loss, function.py:291-296)."""
+    require_cuda(a, b)
+    if a.shape != b.shape or a.dim() < 3:
+        raise ValueError('mse_mean: two [N, J, ...] tensors of one shape expected')
+    return _MSEMean.apply(a, b)
+
+
 # -------------------------------------------------------------- triangulation
 def triangulate_dlt(M, intr, xy, vis=None, undistort=True, view_major=False):
     """M [G, V, 3, 4] f64, intr [G, V, 9] f64, xy [G, V, J, 2] (or [V, G, J, 2] with view_major) f32|f64,
@@ -860,3 +896,89 @@ def pair_mi_loss(u, measure, nseg=1):
     if u.dim() != 3 or u.shape[1] != u.shape[2] or u.shape[0] % nseg:
         raise ValueError('pair_mi_loss: u must be [nseg * N, Q, Q], got %s' % (tuple(u.shape),))
     return _PairMILoss.apply(u.contiguous().float(), MI_MEASURES[measure], nseg)
+
+
+# ------------------------------------------------------------ training-loop metrics
+def _view_pointers(tensors):
+    import ctypes
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _same_maps(views, what):
+    views = [v.detach() for v in views]
+    require_cuda(*views)
+    shape = tuple(views[0].shape)
+    for v in views:
+        if v.dtype != torch.float32 or tuple(v.shape) != shape:
+            raise ValueError('%s: float32 tensors of one shape expected, got %s %s' % (what, v.dtype, tuple(v.shape)))
+    return [v.contiguous() for v in views]
+
+
+def pck_accuracy(outputs, targets, thr=0.5):
+    """PCK accuracy of V views (posu_pck_accuracy): lists of [N, J, H, W] f32 cuda heatmaps ->
+    (acc [V, J + 1] f64, avg [V] f64, cnt [V] int32, pred [V, N, J, 2] f32, step [2] f64 = the means
+    over the views of avg and cnt), all on the device; nothing is read back."""
+    import ctypes
+    if not outputs or len(outputs) != len(targets):
+        raise ValueError('pck_accuracy: one target per output view expected')
+    outs, tgts = _same_maps(outputs, 'pck_accuracy'), _same_maps(targets, 'pck_accuracy')
+    if outs[0].dim() != 4 or tgts[0].shape != outs[0].shape:
+        raise ValueError('pck_accuracy: [N, J, H, W] outputs and targets of one shape expected')
+    v = len(outs)
+    n, j, h, w = outs[0].shape
+    dev = outs[0].device
+    ws_bytes = nat.load().posu_pck_accuracy_workspace(v, n, j)
+    if ws_bytes < 0:
+        raise ValueError('pck_accuracy: unsupported shape V=%d N=%d J=%d (1 to 8 views)' % (v, n, j))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    acc = torch.empty((v, j + 1), dtype=torch.float64, device=dev)
+    avg = torch.empty((v,), dtype=torch.float64, device=dev)
+    cnt = torch.empty((v,), dtype=torch.int32, device=dev)
+    pred = torch.empty((v, n, j, 2), dtype=torch.float32, device=dev)
+    step = torch.empty((2,), dtype=torch.float64, device=dev)
+    po, pt = _view_pointers(outs), _view_pointers(tgts)
+    call('posu_pck_accuracy', ctypes.cast(po, ctypes.c_void_p), ctypes.cast(pt, ctypes.c_void_p), v, n, j, h, w,
+         float(thr), ptr(acc), ptr(avg), ptr(cnt), ptr(pred), ptr(step), ptr(ws), ws_bytes, stream_of(dev))
+    return acc, avg, cnt, pred, step
+
+
+def grad_row_norms(grads, p=1):
+    """sum over the views of (sum of the rows' p-norms / rows with a norm != 0) in f64
+    (posu_grad_row_norms): grads a list of [N, ...] f32 cuda tensors of one shape, None = a view
+    without a gradient (skipped; at least one must be there).  -> 0-dim f64 cuda tensor."""
+    import ctypes
+    have = [g for g in grads if g is not None]
+    if not have:
+        raise ValueError('grad_row_norms: no view has a gradient')
+    if p not in (1, 2):
+        raise ValueError('grad_row_norms: norm order 1 or 2, got %r' % (p,))
+    have = _same_maps(have, 'grad_row_norms')
+    it = iter(have)
+    rows = [None if g is None else next(it) for g in grads]
+    n = have[0].shape[0]
+    length = have[0][0].numel()
+    dev = have[0].device
+    ws_bytes = nat.load().posu_grad_row_norms_workspace(len(rows), n)
+    if ws_bytes < 0:
+        raise ValueError('grad_row_norms: unsupported shape V=%d N=%d (1 to 8 views)' % (len(rows), n))
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    out = torch.empty((), dtype=torch.float64, device=dev)
+    tab = _view_pointers(rows)
+    call('posu_grad_row_norms', ctypes.cast(tab, ctypes.c_void_p), len(rows), n, length, int(p), ptr(out), ptr(ws),
+         ws_bytes, stream_of(dev))
+    return out
+
+
+def meters_update(table, values, weights, active):
+    """AverageMeter.update of every active slot in one launch (posu_meters_update): table [M, 3] f64
+    (val, sum, count) updated in place; values, weights [M] f64 cuda; active: M host booleans."""
+    require_cuda(table, values, weights)
+    m = table.shape[0]
+    for t, shape in ((table, (m, 3)), (values, (m,)), (weights, (m,))):
+        if t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError('meters_update: contiguous float64 table [M, 3], values [M] and weights [M] expected')
+    mask = np.ascontiguousarray(np.asarray(active, dtype=np.uint8))
+    if mask.shape != (m,):
+        raise ValueError('meters_update: one active flag per meter expected')
+    call('posu_meters_update', ptr(table), m, ptr(values), ptr(weights), mask.ctypes.data, stream_of(table.device))
+    return table

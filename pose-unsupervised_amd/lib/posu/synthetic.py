@@ -257,6 +257,71 @@ def heatmap_mi_cfg(sigma=2, channels=256, inter_channels=64, measure='JSD', join
     )
 
 
+# ------------------------------------------------------------ the training loop (core.function.train)
+def train_loop_cfg(num_layers=18, image_size=64, num_joints=16, aggre=False, fuse_output=False, consistent=False,
+                   fundamental=True, watch_grad_norm=True, heatmap_mi=False, print_freq=100, sigma=0,
+                   mi_channels=32, mi_inter_channels=32, mi_measure='JSD', mi_joint_idx=0):
+    """make_cfg plus the fields core.function.train reads (reference lib/core/config.py names; the five
+    losses this build lacks are present and off)."""
+    cfg = make_cfg(num_layers=num_layers, image_size=image_size, num_joints=num_joints)
+    cfg.NETWORK.AGGRE = bool(aggre)
+    cfg.NETWORK.SIGMA = sigma
+    cfg.TEST.FUSE_OUTPUT = bool(fuse_output)
+    cfg.PRINT_FREQ = print_freq
+    L = cfg.LOSS
+    L.USE_FUNDAMENTAL_LOSS = bool(fundamental)
+    L.USE_CONSISTENT_LOSS = bool(consistent)
+    L.CONSISTENT_LOSS_WEIGHT = 0.5
+    L.WATCH_GRAD_NORM = bool(watch_grad_norm)
+    L.USE_HEATMAP_MI_LOSS = bool(heatmap_mi)
+    L.HEATMAP_MI_MEASURE = mi_measure
+    L.HEATMAP_MI_LOSS_WEIGHT = 0.1
+    for flag in ('USE_GLOBAL_MI_LOSS', 'USE_LOCAL_MI_LOSS', 'USE_DOMAIN_TRANSFER_LOSS', 'USE_VIEW_MI_LOSS',
+                 'USE_JOINTS_MI_LOSS'):
+        setattr(L, flag, False)
+    cfg.HEATMAP_DISCRIMINATOR = _ns(INPUT_CHANNELS=mi_channels + 1, INTER_CHANNELS=mi_inter_channels,
+                                    JOINT_IDX=mi_joint_idx)
+    return cfg
+
+
+def train_loop_batches(nbatches, nviews=4, batch=2, image_size=64, num_joints=16, seed=0, sources=None,
+                       target_sigma=1.0):
+    """Seeded batches in the layout the reference's loader hands core.function.train: a list of
+    (input, target, weight, meta), each a list over the views -- input [batch, 3, S, S] N(0, 1), target
+    [batch, J, S/4, S/4] Gaussians at the joints, weight [batch, J, 1] (one joint in ten off), meta dicts
+    with source (default all 'h36m'), subject, center, scale, joints_2d_transformed (input px) and
+    joints_vis.  Everything on the host, like a DataLoader's output."""
+    hm = image_size // 4
+    sources = list(sources) if sources is not None else ['h36m'] * batch
+    assert len(sources) == batch
+    ys, xs = np.meshgrid(np.arange(hm), np.arange(hm), indexing='ij')
+    out = []
+    for b in range(nbatches):
+        r = _rng('train_loop', seed * 1000 + b)
+        subjects = torch.from_numpy(np.array([SUBJECTS[(b + k) % len(SUBJECTS)] for k in range(batch)],
+                                             dtype=np.int64))
+        inputs, targets, weights, meta = [], [], [], []
+        for v in range(nviews):
+            inputs.append(torch.from_numpy(r.standard_normal((batch, 3, image_size, image_size))
+                                           .astype(np.float32)))
+            c = r.uniform(2.0, hm - 3.0, size=(batch, num_joints, 2))    # heatmap px (x, y)
+            g = np.exp(-((xs - c[..., 0, None, None]) ** 2 + (ys - c[..., 1, None, None]) ** 2)
+                       / (2.0 * target_sigma ** 2))
+            vis = (r.uniform(size=(batch, num_joints, 1)) > 0.1).astype(np.float64)
+            targets.append(torch.from_numpy(g.astype(np.float32)))
+            weights.append(torch.from_numpy(vis.astype(np.float32)))
+            meta.append({
+                'source': list(sources),
+                'subject': subjects.clone(),
+                'center': torch.from_numpy(np.array([512.0, 515.0]) + r.uniform(-100.0, 100.0, size=(batch, 2))),
+                'scale': torch.full((batch, 2), 5.0, dtype=torch.float64),
+                'joints_2d_transformed': torch.from_numpy(c * (image_size / hm)),
+                'joints_vis': torch.from_numpy(np.repeat(vis, 3, axis=2)),
+            })
+        out.append((inputs, targets, weights, meta))
+    return out
+
+
 def heatmap_mi_case(seed, n, channels, inter_channels, joint_idx=0, num_joints=16, corners=False, image_size=256):
     """Seeded inputs of one HeatmapMILoss call as float64 numpy arrays: low-level features
     [n, channels, 64, 64], heatmaps [n, J, 64, 64], the meta fields the sampling reads, and the
