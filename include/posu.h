@@ -201,7 +201,8 @@ int posu_conv2d_fwd(int dtype, const void* x, int N, int H, int W, int C,
  *                     * scale + shift )
  * with the two BN scales pre-multiplied into W by the caller.
  *   x: [N, H, W, C]; x2: [N, H2, W2, C2]; C, C2 multiples of posu_conv_bk(dtype);
- *   w: [CoutPad][C + C2]; y: [N, H, W, Cout]. */
+ *   w: [CoutPad][C + C2]; y: [N, H, W, Cout], Cout a multiple of 16 bytes (as in
+ *   posu_conv2d_fwd: the epilogues store whole 16-byte channel chunks). */
 int posu_conv1x1_dual_fwd(int dtype, const void* x, int N, int H, int W, int C,
                           const void* x2, int H2, int W2, int C2, int stride2,
                           const void* w, int Cout, const float* scale, const float* shift,

@@ -420,6 +420,8 @@ extern "C" int posu_conv1x1_dual_fwd(int dtype, const void* x, int N, int H, int
   POSU_REQUIRE(tile_ok(dtype, tile), tile_error("posu_conv1x1_dual_fwd", dtype));
   if (int st = common_checks(dtype, x2, w, y, N, H2, W2, C2, Cout, "posu_conv1x1_dual_fwd")) return st;
   const int BK = bk_of(dtype);
+  // (the NHWC epilogues store whole 16-byte channel chunks, as in posu_conv2d_fwd)
+  POSU_REQUIRE(Cout % (16 / esz_of(dtype)) == 0, "posu_conv1x1_dual_fwd: Cout must be a multiple of 16 bytes");
   POSU_REQUIRE(C % BK == 0 && C2 % BK == 0, "posu_conv1x1_dual_fwd: C and C2 must be multiples of the K-tile");
   POSU_REQUIRE(stride2 > 0 && (H - 1) * stride2 < H2 && (W - 1) * stride2 < W2,
                "posu_conv1x1_dual_fwd: source-2 grid too small for the output grid");

@@ -56,10 +56,11 @@ def pack_rows(views_vm, code):
     return x
 
 
-def gemm_rows(x, wt, ncol, vblk, code):
+def gemm_rows(x, wt, ncol, vblk, code, out=None):
     """out [ncol / vblk, M, vblk] f32 = blocks of x [M, K] . wt^T (wt [ncol, K])."""
     m, k = x.shape
-    out = torch.empty((ncol // vblk, m, vblk), dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((ncol // vblk, m, vblk), dtype=torch.float32, device=x.device)
     call('posu_gemm_rows_f32', code, ptr(x), m, k, ptr(wt), ncol, vblk, ptr(out), stream_of(x.device))
     return out
 

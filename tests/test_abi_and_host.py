@@ -82,6 +82,22 @@ def test_unknown_tiles_are_refused_without_a_gpu():
                 assert n != 3 or 'unknown tile' in err
 
 
+def test_dual_1x1_refuses_a_cout_off_the_16_byte_chunk():
+    """posu_conv1x1_dual_fwd stores whole 16-byte channel chunks like posu_conv2d_fwd: a Cout that is
+    no multiple of 16 bytes (68 channels of 2 bytes, 66 of 4) is refused before any launch -- its last
+    chunk would run into the next pixel -- and 72 / 68 pass that check (null scale / shift, so the
+    next refusal is not about Cout)."""
+    lib = _native.load()
+    p = ctypes.c_void_p(16)
+    for dt, bad in ((_native.BF16, 68), (_native.F16, 68), (_native.F16, 4), (_native.F32, 66), (_native.F32, 2)):
+        st = lib.posu_conv1x1_dual_fwd(dt, p, 1, 8, 8, 64, p, 8, 8, 64, 1, p, bad, None, None, 1, p, -1, None)
+        assert st == 1 and 'Cout must be a multiple of 16 bytes' in _native.last_error(), (dt, bad)
+    for dt, ok in ((_native.BF16, 72), (_native.F32, 68)):
+        # source 2 too small for the output grid: refused further down, past the Cout check
+        st = lib.posu_conv1x1_dual_fwd(dt, p, 1, 8, 8, 64, p, 4, 4, 64, 2, p, ok, None, None, 1, p, -1, None)
+        assert st == 1 and 'source-2 grid too small' in _native.last_error(), (dt, ok)
+
+
 def test_split_pack_layout():
     """packing.to_split: per 32-k block [hi 32 | lo 32], hi = fp16(v 2^e), lo = fp16(v 2^e - hi)."""
     torch.manual_seed(3)

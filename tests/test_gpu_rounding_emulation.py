@@ -20,22 +20,18 @@ not fitted.  Through every stage the emulation carries a bou
     off by at most max |relu(q(v +- D)) - q(relu(v))| -- zero where that interval holds no
     rounding boundary, i.e. such an element must come out EXACT.
 Every kernel output must lie within its bound, and (the regression gate) at most 0.5 % of the
-outputs may sit more than half an ulp from the emulation."""
+outputs may sit more than half an ulp from the emulation.  The emulation itself (_q, _E, _store,
+_conv, _check) lives in tests/conv_emulation.py, shared with the conv family's edge-shape tests."""
 import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_emulation import _E, _check, _conv, _q
 from posu import ops, packing
 from posu._native import BF16
 
 pytestmark = pytest.mark.gpu
 DT = torch.bfloat16
-U32 = 2.0 ** -24
-
-
-def _q(t):
-    """Round an fp64 tensor to bf16 (RNE) and back, as a kernel store does."""
-    return t.float().to(DT).double()
 
 
 def _params(g, c, p):
@@ -47,72 +43,12 @@ def _params(g, c, p):
     return w1, bn(p), w2, bn(p), w3, bn(c)
 
 
-def _col(v):
-    return v.double().view(1, -1, 1, 1)
-
-
-def _gamma(k):
-    return k * U32 / (1 - k * U32)
-
-
-class _E:
-    """An emulated stored tensor (fp64 values, exactly bf16-representable) and its per-element
-    bound d on the kernel's deviation from it."""
-
-    def __init__(self, v, d=None):
-        self.v, self.d = v, torch.zeros_like(v) if d is None else d
-
-
-def _store(v, dv, relu=True):
-    """Round (after ReLU) a pre-rounding value v known to within dv: -> _E."""
-    act = F.relu if relu else (lambda t: t)
-    r = _q(act(v))
-    d = torch.maximum((_q(act(v + dv)) - r).abs(), (_q(act(v - dv)) - r).abs())
-    return _E(r, d)
-
-
-def _conv(srcs, scale, shift, residual=None, relu=True):
-    """sum over (E input, fp64 weight already rounded as packed, stride, padding) of the convs,
-    * scale + shift (+ residual): the emulated stored output and its bound."""
-    v = S = P = 0
-    k = 0
-    for a, w, stride, pad in srcs:
-        v = v + F.conv2d(a.v, w, stride=stride, padding=pad)
-        S = S + F.conv2d(a.v.abs(), w.abs(), stride=stride, padding=pad)
-        P = P + F.conv2d(a.d, w.abs(), stride=stride, padding=pad)
-        k += w.shape[1] * w.shape[2] * w.shape[3]
-    sc = _col(scale) if scale is not None else 1.0
-    v = v * sc + _col(shift)
-    dv = abs(sc) * (P + _gamma(k) * S)
-    if residual is not None:
-        v = v + residual.v
-        dv = dv + residual.d
-    dv = dv + 2 * U32 * (v.abs() + dv)
-    return _store(v, dv, relu)
-
-
 def _emulate_block(xq, w1, bn1, w2, bn2, w3, bn3):
     """xq: NCHW fp64 holding bf16 values.  conv weights rounded to bf16 as packed."""
     x = _E(xq)
     t1 = _conv([(x, _q(w1.double()), 1, 0)], bn1[0], bn1[1])
     t2 = _conv([(t1, _q(w2.double()), 1, 1)], bn2[0], bn2[1])
     return _conv([(t2, _q(w3.double()), 1, 0)], bn3[0], bn3[1], residual=x)
-
-
-def _check(name, got_nhwc, emul):
-    got = got_nhwc.float().cpu().permute(0, 3, 1, 2).double()
-    dev = (got - emul.v).abs()
-    ulp = 2.0 ** -7 * emul.v.abs().clamp_min(2.0 ** -4)
-    r = dev / ulp
-    off = float((r > 0.5).double().mean())
-    exact_req = emul.d == 0
-    print('%s vs bf16-rounding emulation: exact %.4f, >1/2 ulp %.5f, max %.3g ulp; derived bound: %.3f of the '
-          'outputs must be exact, bound max %.3g ulp, largest deviation / bound %.3g'
-          % (name, float((r == 0).double().mean()), off, float(r.max()), float(exact_req.double().mean()),
-             float((emul.d / ulp).max()), float((dev / emul.d.clamp_min(1e-30)).max())))
-    assert torch.isfinite(got).all()
-    assert bool((dev <= emul.d).all()), 'deviation beyond the derived bound at %d elements' % int((dev > emul.d).sum())
-    assert off < 5e-3, off
 
 
 def _dev(xq, cuda):

@@ -36,7 +36,8 @@ DGRAD_CASES = [
     # n, cin, h, w, cout, k, stride, pad
     (2, 64, 16, 16, 64, 3, 1, 1),
     (2, 64, 17, 15, 128, 3, 2, 1),    # strided 3x3, odd input
-    (2, 128, 16, 16, 256, 1, 2, 0),   # downsample 1x1 / s2 (with residual: in place over dy's pixels)
+    (2, 128, 16, 16, 256, 1, 2, 0),   # downsample 1x1 / s2 (out of place here, also with the residual; the
+                                      # in-place path: tests/test_gpu_conv_edges.py::test_data_gradient_in_place)
     (2, 64, 15, 17, 128, 1, 2, 0),    # the same, odd input
     (3, 256, 8, 8, 64, 1, 1, 0),
     (2, 128, 8, 8, 64, 4, 2, 1),      # the deconv's data gradient is this forward conv's shape
