@@ -286,6 +286,25 @@ def test_wide_discriminator_c_m_128(cuda):
     compare(got, ref64, ref32, all_keys(), 'cm128')
 
 
+@pytest.mark.parametrize('n,q,c,cm', [(1, 192, 8, 128), (129, 16, 8, 32), (5, 7, 8, 64)],
+                         ids=['three_b3_slabs', 'two_chunks_per_block', 'one_slab_ragged_waves'])
+def test_pair_walk_edges(cuda, n, q, c, cm):
+    """Walks of the pair passes no other case takes, against the restatement (JSD, training):
+    1 x 192, c_m 128: four j slabs, three in k_b3 (its dA buffers summed by k_sum_slabs);
+    129 x 16, c_m 32: 33 chunks over 32 blocks, block 0 walks two (k_b2 / k_b3 re-zero their per-chunk
+    state, k_b3 overwrites A in place between them);
+    5 x 7, c_m 64: one slab whose 7 values of j are no multiple of the four waves.
+    Positions are seeded draws with one repeated per image."""
+    spec = dict(n=n, c=c, cm=cm, sigma=0, joint=1)
+    case = syn.heatmap_mi_case(900 + q, n, c, cm, joint_idx=1)
+    idx = np.random.default_rng(q).integers(0, 64 * 64, (n, q)).astype(np.int32)
+    idx[:, -1] = idx[:, 0]
+    # one use each: not through references(), whose cache is keyed on the identity of a case that lives on
+    ref64, ref32 = (R.evaluate(case, idx, 1, 'JSD', True, dt, cuda, None) for dt in (torch.float64, torch.float32))
+    got = run_fused(case, spec, idx, 'JSD', cuda)
+    compare(got, ref64, ref32, all_keys(), 'walk %dx%d cm%d' % (n, q, cm))
+
+
 def test_micro_step_moves_the_discriminator(cuda):
     """views() over four synthetic 64 x 64 views, backward, one posu.optim.Adam step on the
     discriminator (no backbone of the suite has 64 x 64 maps at a size it trains cheaply)."""

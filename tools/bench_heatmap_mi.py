@@ -11,9 +11,21 @@ on the same device, in the same process, alternating the two.  Prints one JSON l
 per step (median and spread over the repeats, host clock around a device synchronise) and
 torch.cuda.max_memory_allocated of each side's step.  Needs a GPU; there is no CPU path.
 
-    python tools/bench_heatmap_mi.py [--views 4 --batch 8 --repeats 5 --iters 10 --features bf16]
+    python tools/bench_heatmap_mi.py [--views 4 --batch 8 --repeats 5 --iters 10 --features bf16] [--lib PATH]
+
+--lib PATH loads another build of libposeu.so (two builds, alternated by the caller, are how a change
+to the kernels is timed against its parent).
+
+    python tools/bench_heatmap_mi.py --digest [--lib PATH]
+
+No timing: ops.heatmap_pair_scores and both measures at small fixed shapes (DIGEST_SHAPES: one and
+two segments, every c_m, every j-slab count of the pair passes, a block that walks two chunks,
+Q = 1), seeded inputs and indices with a repeated position per image; f32 / bf16 / f16 features,
+train and eval, inputs attached and detached, the discriminator frozen; one sha1 per output tensor.
+Two builds compute the same bits when their listings are equal line for line.
 """
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -26,8 +38,68 @@ for p in (os.path.join(REPO, 'pose-unsupervised_amd', 'lib'), os.path.join(REPO,
         sys.path.insert(0, p)
 
 
+# (S, N, Q, C, c_m): what each reaches is in DESIGN.md section 4 (JS = max(1, min(4, Q / 8)) j slabs,
+# k_b3 the largest JS3 <= JS with JS3 c_m <= 2 Q; 64 rows per chunk, at most 32 blocks per slab)
+DIGEST_SHAPES = [(1, 3, 18, 32, 32), (2, 3, 18, 32, 32), (1, 2, 216, 256, 64), (1, 2, 18, 16, 128),
+                 (1, 1, 128, 8, 128), (1, 1, 192, 8, 128), (1, 129, 16, 8, 32), (1, 5, 7, 8, 64),
+                 (1, 37, 1, 32, 32)]
+
+
+def digest_indices(seed, rows, q):
+    """Seeded positions [rows, q] of a 64 x 64 map; position 0 of every image repeats at the end."""
+    import numpy as np
+    idx = np.random.default_rng(seed).integers(0, 64 * 64, (rows, q)).astype(np.int32)
+    if q > 1:
+        idx[:, -1] = idx[:, 0]
+    return idx
+
+
+def digest():
+    import torch
+    from models.discriminator import HeatmapDiscriminator
+    from posu import ops
+    from posu import synthetic as syn
+
+    dev = torch.device('cuda', 0)
+
+    def sha(t):
+        return hashlib.sha1(t.detach().contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()[:12]
+
+    for s, n, q, c, cm in DIGEST_SHAPES:
+        joint = 1
+        case = syn.heatmap_mi_case(500 + q + cm, s * n, c, cm, joint_idx=joint)
+        idx = torch.as_tensor(digest_indices(600 + q + cm, s * n, q))
+        disc = HeatmapDiscriminator(syn.heatmap_mi_cfg(channels=c, inter_channels=cm, joint_idx=joint))
+        disc.load_state_dict({k: torch.as_tensor(v) for k, v in case['state'].items()})
+        disc = disc.to(dev)
+        low32 = torch.as_tensor(case['low_features']).to(dev).float()
+        heat0 = torch.as_tensor(case['heatmaps']).to(dev).float()
+        runs = [(dt, training, attach, False) for dt in (torch.float32, torch.bfloat16, torch.float16)
+                for training in (True, False) for attach in (True, False)]
+        runs.append((torch.float32, True, True, True))     # dparams null: k_b2 without the d W2 sums
+        for dt, training, attach, frozen in runs:
+            low = low32.to(dt).permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2).requires_grad_(attach)
+            heat = heat0.clone().requires_grad_(attach)
+            params = {k: (v.detach().clone() if frozen else v.detach().clone().requires_grad_(
+                v.is_floating_point() and k not in ('rm1', 'rv1', 'rm2', 'rv2'))) for k, v in disc._params().items()}
+            u, stats = ops.heatmap_pair_scores(low, heat, idx, joint, params, nseg=s, training=training)
+            nce = ops.pair_mi_loss(u, 'NCE', s)
+            jsd = ops.pair_mi_loss(u, 'JSD', s) if q > 1 else None    # JSD has no off-diagonal pair at Q = 1
+            (nce.sum() if jsd is None else nce.sum() + jsd.sum()).backward()
+            torch.cuda.synchronize()
+            outs = [('u', u), ('jsd', jsd), ('nce', nce), ('stats', stats if training else None),
+                    ('dlow', low.grad), ('dheat', heat.grad)]
+            outs += [('d' + k, p.grad) for k, p in params.items()]
+            tag = 'S%d N%d Q%d C%d cm%d %s %s %s%s' % (s, n, q, c, cm, str(dt).split('.')[1],
+                                                      'train' if training else 'eval',
+                                                      'attached' if attach else 'detached', ' frozen' if frozen else '')
+            print('%-52s %s' % (tag, ' '.join('%s=%s' % (k, sha(t)) for k, t in outs if t is not None)))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--lib', default=None, help='another build of libposeu.so')
+    ap.add_argument('--digest', action='store_true', help='no timing: one sha1 per output tensor at small shapes')
     ap.add_argument('--views', type=int, default=4)
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--channels', type=int, default=256)
@@ -39,6 +111,11 @@ def main():
     ap.add_argument('--iters', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     args = ap.parse_args()
+    if args.lib:
+        from posu import _native
+        _native._LIB_PATH = os.path.abspath(args.lib)
+    if args.digest:
+        return digest()
 
     import torch
     import heatmap_mi_restatement as R
