@@ -25,34 +25,10 @@
 // hit 16 distinct chunk slots.
 // MFMA operands swapped (A = weights, B = pixels): lane (r16, q) accumulates channels 4q .. 4q+3
 // of pixel r16; v_permlane16_swap pairs the 2 n-tiles into 8 consecutive channels.
-#include <type_traits>
-
-#include "gemm_common.h"
+#include "tail_common.h"
 
 namespace posu {
 namespace {
-
-struct TailS2Geom {
-  const void* t1;
-  const void* x;
-  void* y;
-  const uint4* wst;   // [4 channel groups][kSteps][2 n-tiles][64 lanes] x 16 B
-  const float* s2;
-  const float* b2;
-  const float* shift;  // b3 + bd [512]
-  int N, Hin;
-  // NEXT (chained): the next identity block's conv1 + BN1 + ReLU over y while it is produced
-  // (t1n = relu(y conv1n * s1n + b1n), [N][Hin/2][32][128])
-  const float* s1n;
-  const float* b1n;
-  void* t1n;
-  long long wseg;  // the weight stream's 64-B segments (warm-up, gemm_common.h)
-  int warm;        // warm-up workgroups (0: none)
-};
-
-#ifndef POSU_S2_KD
-#define POSU_S2_KD 4
-#endif
 
 template <bool NEXT>
 struct S2Cfg {
@@ -74,7 +50,7 @@ struct S2Cfg {
   static constexpr int kSteps2 = 9 * kKT, kStepsC = kKT + kKX + (NEXT ? kKT : 0);
   static constexpr int kSteps = kSteps2 + kNC * kStepsC;                  // 36 + 4 x 12 = 84 (NEXT: 100)
   static constexpr int kYC = kShift + kCout * 4;                          // NEXT: the y chunk [64 px][128 ch]
-  static constexpr int kD = POSU_S2_KD;
+  static constexpr int kD = 4;                                            // weight prefetch depth (k-steps)
   static_assert(kYC + (NEXT ? kPx * kRowB : 0) <= kBN2, "t2, the x pixels, the shift (and the y chunk) fit over the window");
   static_assert(2 * kLds <= 160 * 1024, "two workgroups per CU");
   static_assert(kKT % kD == 0 && kKX % kD == 0 && kSteps2 % kD == 0 && kStepsC % kD == 0,
@@ -82,17 +58,17 @@ struct S2Cfg {
 };
 
 template <typename T, bool NEXT>
-__global__ __launch_bounds__(S2Cfg<NEXT>::kNW * 64, 2) void tail_s2_kernel(TailS2Geom g) {
+__global__ __launch_bounds__(S2Cfg<NEXT>::kNW * 64, 2) void tail_s2_kernel(TailGeom g) {
   using O = Op<T>;
   using K = S2Cfg<NEXT>;
-  constexpr int ES = 2, kD = K::kD, MT = K::kRows;
+  constexpr int ES = 2, MT = K::kRows;
   __shared__ __attribute__((aligned(16))) char smem[K::kLds];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int r16 = lane & 15, q = lane >> 4;
   const int cq = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned lds0 = static_cast<unsigned>(reinterpret_cast<size_t>((__attribute__((address_space(3))) char*)smem));
-  const int Hin = g.Hin, Hout = Hin / 2;
+  const int Hin = g.H, Hout = Hin / 2;
   const int tiles_x = K::kWout / K::kTW, tiles_y = Hout / K::kRows;
   const int n = blockIdx.x / (tiles_x * tiles_y);
   const int rem = blockIdx.x - n * tiles_x * tiles_y;
@@ -123,79 +99,16 @@ __global__ __launch_bounds__(S2Cfg<NEXT>::kNW * 64, 2) void tail_s2_kernel(TailS
     }
   }
 
-  // ---- the weight stream of channel group cq (prefetches past the end reload the last k-step)
-  const char* wst = reinterpret_cast<const char*>(g.wst) + cq * (K::kSteps * 2 * 1024);
-  const int wlane = lane * 16;
-  auto frag = [&](int p, int j) -> const uint4* {
-    return reinterpret_cast<const uint4*>(wst + (min(p, K::kSteps - 1) * 2 + j) * 1024 + wlane);
-  };
-  uint4 wa[kD][2];
-#pragma unroll
-  for (int d = 0; d < kD; ++d) {
-    wa[d][0] = *frag(d, 0);
-    wa[d][1] = *frag(d, 1);
-  }
-  unsigned wv[kWarmLoads];   // the stream's warm-up (gemm_common.h)
-  warm_issue(wv, g.wst, g.wseg, g.warm, K::kNW * 64);
-  vm_wait<0>();  // the window (LDS-DMA) and the first fragments
-  warm_use(wv);
-  lds_barrier();
+  // ---- the weight stream of channel group cq; the window (LDS-DMA) and the first fragments
+  WStream<K::kD, K::kSteps> ws(g.wst, cq, lane);
+  ws.start(g, K::kNW * 64);
 
   f32x4 acc[MT][2];
   f32x4 acc1[MT][2];  // NEXT: the next conv1's accumulators over the whole chunk loop
-  auto zero = [&](f32x4 (&a)[MT][2]) {
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) a[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  };
-  auto pair = [&](const f32x4 (&a)[MT][2], int i, float* v) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(a[i][0][e]), __float_as_uint(a[i][1][e]),
-                                                       false, false);
-      v[e] = __uint_as_float(sw[0]);
-      v[4 + e] = __uint_as_float(sw[1]);
-    }
-  };
-  const int cpair = 16 * (q & 1) + 8 * (q >> 1);
-  // NS k-steps (stream k-steps p0 .., p0 a multiple of kD: the ring slot of k-step d is the
-  // compile-time d % kD) over an LDS image of RB-byte pixel rows: k-step d reads, for
-  // m-tile i, the pixel lpix + coff(i) at 16-B chunk 4 d + q, XOR the lane's key (its LDS
-  // column & 15).  The pixel fragments of k-step d + 1 are read while k-step d's MFMAs run.
-  auto block = [&](f32x4 (&acc)[MT][2], auto nsteps, auto rowb, int p0, int base, int lpix, int key, auto coff) {
-    constexpr int NS = decltype(nsteps)::value, RB = decltype(rowb)::value;
-    uint4 b[2][MT];
-    const char* lb = smem + base + lpix * RB + ((q ^ (key & 3)) << 4);
-    const char* kb[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) kb[k] = lb + ((k ^ (key >> 2)) << 6);
-    auto rd = [&](int i, int d) -> uint4 {
-      return *reinterpret_cast<const uint4*>(kb[d & 3] + coff(i) * RB + (d & 4) * 64);
-    };
-#pragma unroll
-    for (int i = 0; i < MT; ++i) b[0][i] = rd(i, 0);
-#pragma unroll
-    for (int d = 0; d < NS; ++d) {
-      if (d + 1 < NS) {
-#pragma unroll
-        for (int i = 0; i < MT; ++i) b[(d + 1) & 1][i] = rd(i, d + 1);
-      }
-      const int s = d % kD;
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) O::mma(acc[i][j], wa[s][j], b[d & 1][i]);
-      const int p = p0 + d + kD;
-      wa[s][0] = *frag(p, 0);
-      wa[s][1] = *frag(p, 1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  using NKT = std::integral_constant<int, K::kKT>;
-  using NKX = std::integral_constant<int, K::kKX>;
-  using RBT = std::integral_constant<int, K::kRowB>;
-  using RBX = std::integral_constant<int, K::kXRowB>;
+  const int c32 = 32 * cq + cpair(q);   // this lane's 8 channels of the wave's 32
+  using Win = Stride2Addr<K::kRowB, K::kWC>;
+  using T2 = RowsAddr<K::kRowB, K::kTW, K::kTW>;    // t2 and the y chunk: [64 px][128 ch]
+  using XI = RowsAddr<K::kXRowB, K::kTW, K::kTW>;   // the stride-2 x pixels: [64 px][256 ch]
 
   // ---- conv2: 9 taps x 4 channel steps; m-tile i = output row i: window row 2 i + dy, column
   // 2 r16 + dx
@@ -203,8 +116,7 @@ __global__ __launch_bounds__(S2Cfg<NEXT>::kNW * 64, 2) void tail_s2_kernel(TailS
 #pragma unroll 1
   for (int t = 0; t < 9; ++t) {
     const int dy = t / 3, dx = t - 3 * (t / 3);
-    block(acc, NKT{}, RBT{}, K::kKT * t, 0, dy * K::kWC + 2 * r16 + dx, (2 * r16 + dx) & 15,
-          [&](int i) { return 2 * i * K::kWC; });
+    kblock<O, K::kKT, 2>(acc, ws, K::kKT * t, Win(smem, dy, dx, r16, q));
   }
   // every wave is done reading the window: the tile's stride-2 x pixels are DMA'd over it while
   // BN2 + ReLU write t2 beside them
@@ -223,23 +135,16 @@ __global__ __launch_bounds__(S2Cfg<NEXT>::kNW * 64, 2) void tail_s2_kernel(TailS
   }
   {
     float* shl = reinterpret_cast<float*>(smem + K::kShift);
-    for (int c = tid; c < K::kCout; c += K::kNW * 64) shl[c] = g.shift[c];
-    const int c0 = 32 * cq + cpair;
+    for (int c = tid; c < K::kCout; c += K::kNW * 64) shl[c] = g.b3[c];
     float sc[8], sh[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      sc[e] = bn2[c0 + e];
-      sh[e] = bn2[K::kP + c0 + e];
-    }
+    ld8(bn2 + c32, sc);
+    ld8(bn2 + K::kP + c32, sh);
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
       float v[8];
       pair(acc, i, v);
-      affine8<false>(v, sc, sh);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-      *reinterpret_cast<uint4*>(smem + K::kT2 + (16 * i + r16) * K::kRowB + (((c0 >> 3) ^ r16) << 4)) =
-          O::store_vals(v);
+      bn_relu(v, sc, sh, nullptr);
+      lds_store8<O, K::kRowB>(smem + K::kT2, 16 * i + r16, r16, c32 >> 3, v);
     }
   }
   vm_wait<0>();  // the x DMA (and the weight prefetches)
@@ -254,12 +159,11 @@ __global__ __launch_bounds__(S2Cfg<NEXT>::kNW * 64, 2) void tail_s2_kernel(TailS
   for (int nc = 0; nc < K::kNC; ++nc) {
     const int p0 = K::kSteps2 + K::kStepsC * nc;
     zero(acc);
-    block(acc, NKT{}, RBT{}, p0, K::kT2, r16, r16, [&](int i) { return 16 * i; });
-    block(acc, NKX{}, RBX{}, p0 + K::kKT, K::kX, r16, r16, [&](int i) { return 16 * i; });
-    const int c0 = 128 * nc + 32 * cq + cpair;
+    kblock<O, K::kKT, 2>(acc, ws, p0, T2(smem + K::kT2, r16, r16, q));
+    kblock<O, K::kKX, 2>(acc, ws, p0 + K::kKT, XI(smem + K::kX, r16, r16, q));
+    const int c0 = 128 * nc + c32;
     float sh[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) sh[e] = shl[c0 + e];
+    ld8(shl + c0, sh);
     if constexpr (NEXT) {
       if (nc > 0) lds_barrier();  // every wave is done reading the previous y chunk
     }
@@ -271,38 +175,30 @@ __global__ __launch_bounds__(S2Cfg<NEXT>::kNW * 64, 2) void tail_s2_kernel(TailS
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
       const size_t pix = (static_cast<size_t>(n) * Hout + R0 + i) * K::kWout + C0 + r16;
-      const uint4 o = O::store_vals(v);
-      *reinterpret_cast<uint4*>(yg + pix * K::kCout + c0) = o;
+      *reinterpret_cast<uint4*>(yg + pix * K::kCout + c0) = O::store_vals(v);
       // NEXT: the chunk's y (the rounded values just stored), laid out like t2
-      if constexpr (NEXT)
-        *reinterpret_cast<uint4*>(smem + K::kYC + (16 * i + r16) * K::kRowB + ((((c0 & 127) >> 3) ^ r16) << 4)) = o;
+      if constexpr (NEXT) lds_store8<O, K::kRowB>(smem + K::kYC, 16 * i + r16, r16, c32 >> 3, v);
     }
     if constexpr (NEXT) {
       // the next block's conv1 over this K slice (y channels 128 nc ..): the k order of a conv
       // launch over y, so t1n is bit-identical to it
       lds_barrier();
-      block(acc1, NKT{}, RBT{}, p0 + K::kKT + K::kKX, K::kYC, r16, r16, [&](int i) { return 16 * i; });
+      kblock<O, K::kKT, 2>(acc1, ws, p0 + K::kKT + K::kKX, T2(smem + K::kYC, r16, r16, q));
     }
   }
   if constexpr (NEXT) {
     // t1n = relu(conv1n * s1n + b1n): this lane's 8 channels of each m-tile's pixel
     T* tg = reinterpret_cast<T*>(g.t1n);
-    const int c0 = 32 * cq + cpair;
     float sc[8], sh[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      sc[e] = g.s1n[c0 + e];
-      sh[e] = g.b1n[c0 + e];
-    }
+    ld8(g.s1n + c32, sc);
+    ld8(g.b1n + c32, sh);
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
       float v[8];
       pair(acc1, i, v);
-      affine8<false>(v, sc, sh);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+      bn_relu(v, sc, sh, nullptr);
       const size_t pix = (static_cast<size_t>(n) * Hout + R0 + i) * K::kWout + C0 + r16;
-      *reinterpret_cast<uint4*>(tg + pix * K::kP + c0) = O::store_vals(v);
+      *reinterpret_cast<uint4*>(tg + pix * K::kP + c32) = O::store_vals(v);
     }
   }
 }
@@ -320,39 +216,15 @@ int s2_tail_impl(const char* name, int dtype, const void* t1, const void* x, int
   const bool next = t1n != nullptr;
   using K = S2Cfg<false>;
   POSU_REQUIRE(dtype == POSU_BF16 || dtype == POSU_F16, what + ": dtype must be BF16 or F16");
-  POSU_REQUIRE(t1 && x && wstream && s2 && b2 && shift && y, what + ": null pointer");
-  POSU_REQUIRE(y != x && y != t1, what + ": the output must not alias an input");
-  POSU_REQUIRE(!next || (s1n && b1n && t1n != y && t1n != x && t1n != t1),
-               what + ": the next conv1 needs its BN and an output that aliases no other operand");
+  TailGeom g;
+  if (int e = tail_operands(g, what, t1, x, N, H, wstream, wstream_bytes, s2, b2, nullptr, shift, y, s1n, b1n, t1n))
+    return e;
   POSU_REQUIRE(W == K::kWin && C == K::kC && P == K::kP && Cout == K::kCout,
                what + ": built for the first Bottleneck of layer2 of PoseResNet at 256x256 (input W = 64, C = 256, "
                       "planes = 128, output channels 512)");
-  POSU_REQUIRE(N > 0 && H > 0 && H % (2 * K::kRows) == 0,
-               what + ": H must be a positive multiple of " + std::to_string(2 * K::kRows));
-  POSU_REQUIRE(static_cast<long long>(N) * H * W * C * 2 < (1LL << 31) - 256,
-               what + ": activation exceeds the 2 GiB addressing range");
   const long long need = static_cast<long long>(K::kNW) * (next ? S2Cfg<true>::kSteps : K::kSteps) * 2 * 1024;
-  POSU_REQUIRE(wstream_bytes == need, what + ": wstream holds " + std::to_string(wstream_bytes) + " bytes, the " +
-                                          (next ? "chained" : "plain") + " kernel reads " + std::to_string(need));
-  for (const void* p : {t1, x, static_cast<const void*>(y), wstream, static_cast<const void*>(shift),
-                        next ? t1n : t1, static_cast<const void*>(next ? s1n : shift),
-                        static_cast<const void*>(next ? b1n : shift)})
-    POSU_REQUIRE((reinterpret_cast<size_t>(p) & 15) == 0, what + ": pointers must be 16-byte aligned");
-  TailS2Geom g{};
-  g.t1 = t1;
-  g.x = x;
-  g.y = y;
-  g.wst = static_cast<const uint4*>(wstream);
-  g.s2 = s2;
-  g.b2 = b2;
-  g.shift = shift;
-  g.N = N;
-  g.Hin = H;
-  g.s1n = s1n;
-  g.b1n = b1n;
-  g.t1n = t1n;
-  g.wseg = wstream_bytes / 64;
-  g.warm = warm_wgs(wstream_bytes);
+  if (int e = tail_sizes(g, what, 2 * K::kRows, static_cast<long long>(N) * H * W * C * 2, wstream_bytes, need))
+    return e;
   const dim3 grid(static_cast<unsigned>(N * (H / 2 / K::kRows) * (K::kWout / K::kTW)));
   hipStream_t s = as_stream(stream);
   if (dtype == POSU_BF16) {

@@ -354,6 +354,27 @@ def test_fused_bottleneck_refuses_unsupported_shapes(cuda):
                                        torch.zeros(128, 512, device=cuda, dtype=torch.bfloat16))
     with pytest.raises(RuntimeError, match='wstream holds'):
         ops.bottleneck_s2_tail_nhwc(ts, xs, ps2n, sh, sh, sh, BF16)
+    # shapes that have no variant: the split dtype at a 384x384 map, a next-layer conv1 (2 P outputs)
+    # at one, and the downsample tail anywhere but layer1
+    xw = torch.zeros(1, 2, 48, 512, device=cuda, dtype=torch.bfloat16)
+    tw = torch.zeros(1, 2, 48, 128, device=cuda, dtype=torch.bfloat16)
+    with pytest.raises(RuntimeError, match='256x256 tails'):
+        ops.bottleneck_tail_stream_nhwc(torch.zeros(1, 2, 48, 256, device=cuda, dtype=torch.float16),
+                                        torch.zeros(1, 2, 48, 1024, device=cuda, dtype=torch.float16), p2, s2, s2, s2,
+                                        s2, ops.F16X3)
+    with pytest.raises(RuntimeError, match='chained by the 256x256 identity tails only'):
+        ops.bottleneck_tail_stream_chain_nhwc(tw, xw, p2n, s2, s2, s2, s2, s, s, BF16)   # s: Pn = 256 = 2 P
+    with pytest.raises(RuntimeError, match="layer1's first Bottleneck"):
+        ops.bottleneck_down_tail_stream_nhwc(t2[:, :4], t2[:, :4], p2, s2, s2, s2, s2, BF16)
+    # layer3's 4-row tiles run while N (H / 8) < 256 and H % 4 == 0: at H = 12, N = 255 is accepted (one
+    # launch over zeros) and N = 256 takes the 8-row tiles, which H = 12 does not divide into
+    x3n = torch.zeros(256, 12, 16, 1024, device=cuda, dtype=torch.bfloat16)
+    t3n = torch.zeros(256, 12, 16, 256, device=cuda, dtype=torch.bfloat16)
+    y3n = ops.bottleneck_tail_stream_nhwc(t3n[:255], x3n[:255], p3, s3, s3, s3, s3, BF16)
+    torch.cuda.synchronize()
+    assert y3n.shape == (255, 12, 16, 1024)
+    with pytest.raises(RuntimeError, match='multiple of 8'):
+        ops.bottleneck_tail_stream_nhwc(t3n, x3n, p3, s3, s3, s3, s3, BF16)
 
 
 @pytest.mark.parametrize('precision', ['bf16', 'fp16'])

@@ -3,7 +3,7 @@ conv2 (3x3 / stride 2) + the conv3 | downsample dual GEMM as two launches (the p
 tiles are not used: heuristic tiles) vs posu_bottleneck_s2_tail_fwd; HIP events, min over rounds,
 outputs checked bit for bit.
 
-    python tools/s2tail_micro.py [--n 128] [--reps 20] [--rounds 3]
+    python tools/s2tail_micro.py [--n 128] [--reps 20] [--rounds 3] [--lib PATH]
 """
 import argparse
 import os
@@ -39,7 +39,11 @@ def main():
     ap.add_argument('--n', type=int, default=128)
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--lib', default=None)
     a = ap.parse_args()
+    if a.lib:
+        from posu import _native
+        _native._LIB_PATH = os.path.abspath(a.lib)
     dev = torch.device('cuda', 0)
     dt = torch.bfloat16
     g = torch.Generator().manual_seed(0)
