@@ -77,7 +77,8 @@ const char* posu_last_error(void);
  * (posu_rpsm_*) and fp16 training's loss-scaling ones (posu_grad_stats, posu_grad_stats_workspace,
  * posu_adam_step_dev, posu_loss_scale_update) are additive to 16: new symbols only, the revision
  * does not move; so are the heatmap mutual-information ones and the training loop's metrics
- * (posu_pck_accuracy, posu_grad_row_norms, posu_meters_update and their workspace queries).  The
+ * (posu_pck_accuracy, posu_grad_row_norms, posu_meters_update and their workspace queries) and the
+ * 3-D evaluation protocol (posu_procrustes, posu_pose3d_errors, posu_limb_break).  The
  * ctypes binding refuses a library of another revision. */
 int posu_abi_version(void);
 
@@ -886,6 +887,50 @@ int posu_grad_row_norms(const float* const* grads, int V, int N, long long L, in
  * the host's float arithmetic; avg = sum / count is left to the reader. */
 int posu_meters_update(double* table, int M, const double* v, const double* w, const unsigned char* active,
                        void* stream);
+
+/* ------------------------------------------------- 3-D evaluation protocol */
+/* run/pose3d/estimate.py's arithmetic in fp64 (csrc/pose3d.hip), additive to ABI 16.  One wave per
+ * pose, lanes stride over the joints (any J >= 1); every pointer is a device pointer.
+ *
+ * PoseUtils.procrustes (lib/utils/pose_utils.py:61-143) for N pose pairs: B is moved onto the
+ * target A.  In the reference's order: subtract the means, ssX / ssY and the norms, divide by them,
+ * M = A0^T B0, SVD (one-sided Jacobi, at most 30 sweeps), R = V U^T, S_trace = sum s; with scaling
+ * scale = S_trace * normA / normB, d = 1 - S_trace^2, Z = normA * S_trace * B0 R + meanA, without it
+ * scale = 1, d = 1 + ssY / ssX - 2 S_trace normB / normA, Z = normB * B0 R + meanA;
+ * t = meanA - scale * meanB R, so Z = scale * B R + t.
+ *   A, B:  [N, J, 3] f64;
+ *   scaling: 0 / 1;
+ *   reflection: 0 = 'best' (R as it comes), 1 = force a reflection (det R < 0), 2 = forbid one; the
+ *          forced fix negates the column of V and the singular value that belong to the smallest
+ *          singular value, then R = V U^T again (pose_utils.py:111-119);
+ *   d [N], Z [N, J, 3], R [N, 3, 3], scale [N], t [N, 3] f64: each may be NULL, not all of them.
+ * A pose whose joints all coincide (ssX or ssY = 0) gives NaN, as the reference's 0 / 0 does.  With
+ * coplanar joints (M of rank 2) U is completed by a cross product where LAPACK picks a sign: the
+ * sign reaches Z only when the target alone is planar, as it does in the reference; collinear joints
+ * (rank 1) have no defined result. */
+int posu_procrustes(const double* A, const double* B, int N, int J, int scaling, int reflection, double* d,
+                    double* Z, double* R, double* scale, double* t, void* stream);
+
+/* error_computing_3d (estimate.py:110-123) for G groups x V cameras: per (group, camera)
+ * pred = (R (X^T - T))^T; with procrustes != 0, pred <- Z of procrustes(gt, pred) (scaling on,
+ * reflection 'best'); err[g][v][j] = || gt - pred ||.
+ *   X:   [G, J, 3] f64, world frame;
+ *   gt:  [G, V, J, 3] f64, every camera's frame;
+ *   R:   [G, V, 3, 3] f64;  T: [G, V, 3] f64 (the camera centre, world frame);
+ *   err: [G, V, J] f64;  aligned: NULL or [G, V, J, 3] f64, receives pred. */
+int posu_pose3d_errors(const double* X, const double* gt, const double* R, const double* T, int G, int V,
+                       int J, int procrustes, double* err, double* aligned, void* stream);
+
+/* break_limb_length (estimate.py:84-96) for G poses: flag[g] = 1 iff some edge (parent[c], c) has
+ * | limb[c] - || X_p - X_c || | > thres * limb[c] (strict; a NaN never flags, as in numpy), else 0.
+ *   X:      [G, J, 3] f64;
+ *   parent: [J] int32, -1 at the root (an entry outside [0, J) is no edge);
+ *   limb:   expected lengths by child joint: [G, J] with limb_stride = J, or one shared [J] with
+ *           limb_stride = 0;
+ *   flag:   [G] uint8;  worst: NULL or [G] f64, the largest offset / limb over the edges (NaN
+ *           ratios are passed over; 0 without edges). */
+int posu_limb_break(const double* X, const int* parent, const double* limb, int limb_stride, int G, int J,
+                    double thres, unsigned char* flag, double* worst, void* stream);
 
 #ifdef __cplusplus
 }

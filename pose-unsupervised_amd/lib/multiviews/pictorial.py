@@ -255,12 +255,16 @@ def rpsm_batch(camera_params, heatmaps, boxes, grid_centers, limb_lengths, pairw
     [G, J] by child joint), or a single dict / [J] shared by all groups; pairwise_constraint, shared by the
     groups: the reference's dict or a PackedPairwise -> poses [G, J, 3] float64 (with
     return_levels also [RECUR_DEPTH + 1, G, J, 3]: the pose after level 1 and every refinement).
-    A cuda heatmaps tensor is read in place and the result stays on its device; numpy in, numpy out."""
+    A cuda heatmaps tensor is read in place and the result stays on its device; numpy in, numpy out.
+    grid_centers given as a cuda tensor are used where they are (no read-back)."""
     on_device = isinstance(heatmaps, torch.Tensor)
     dev = heatmaps.device if on_device else _device()
-    centers = np.asarray(grid_centers.cpu() if isinstance(grid_centers, torch.Tensor) else grid_centers,
-                         dtype=np.float64).reshape(-1, 3)
-    groups = centers.shape[0]
+    if isinstance(grid_centers, torch.Tensor) and grid_centers.is_cuda:   # used in place: no read-back
+        cdev = grid_centers.to(device=dev, dtype=torch.float64).reshape(-1, 3).contiguous()
+    else:
+        cdev = _dev_f64(np.asarray(grid_centers.cpu() if isinstance(grid_centers, torch.Tensor) else grid_centers,
+                                   dtype=np.float64).reshape(-1, 3), dev)
+    groups = cdev.shape[0]
     if groups == 0 or len(camera_params) % groups or len(boxes) != len(camera_params):
         raise ValueError('%d cameras and %d boxes do not split into %d groups' % (len(camera_params), len(boxes),
                                                                                  groups))
@@ -278,7 +282,6 @@ def rpsm_batch(camera_params, heatmaps, boxes, grid_centers, limb_lengths, pairw
     limbs = _dev_f64(_limb_rows(limb_lengths, tree, groups), dev)
     rows = _dev_f64(_camera_rows(camera_params), dev).reshape(groups, views, 20)
     aff = _dev_f64(_affines(boxes, image_size), dev).reshape(groups, views, 2, 3)
-    cdev = _dev_f64(centers, dev)
     step = 65535 // tree.njoints          # groups per enqueue (the launch grid's extent)
     outs = [ops.rpsm_run(hm[a:a + step], rows[a:a + step], aff[a:a + step], image_size, cdev[a:a + step],
                          float(ps.GRID_SIZE), int(ps.FIRST_NBINS), int(ps.RECUR_NBINS), int(ps.RECUR_DEPTH),

@@ -126,6 +126,10 @@ _SIGNATURES = {
     'posu_grad_row_norms_workspace': [_i, _i],
     'posu_grad_row_norms': [_p, _i, _i, _ll, _i, _p, _p, _ll, _p],
     'posu_meters_update': [_p, _i, _p, _p, _p, _p],
+    # 3-D evaluation protocol (additive to ABI 16)
+    'posu_procrustes': [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p],
+    'posu_pose3d_errors': [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p],
+    'posu_limb_break': [_p, _p, _p, _i, _i, _i, _d, _p, _p, _p],
 }
 _RESTYPES = {'posu_last_error': ctypes.c_char_p, 'posu_conv2d_wgrad_workspace': ctypes.c_longlong,
              'posu_pack_job_blocks': ctypes.c_longlong,

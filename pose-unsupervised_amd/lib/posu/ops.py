@@ -982,3 +982,74 @@ def meters_update(table, values, weights, active):
         raise ValueError('meters_update: one active flag per meter expected')
     call('posu_meters_update', ptr(table), m, ptr(values), ptr(weights), mask.ctypes.data, stream_of(table.device))
     return table
+
+
+# ------------------------------------------------------ 3-D evaluation protocol
+_REFLECTION = {'best': 0, True: 1, False: 2}   # posu_procrustes' reflection codes (include/posu.h)
+
+
+def _f64(t):
+    return t.detach().to(torch.float64).contiguous()
+
+
+def procrustes(A, B, scaling=True, reflection='best'):
+    """PoseUtils.procrustes for a batch (posu_procrustes): A (target), B [N, J, 3] cuda, any float dtype
+    -> (d [N], Z [N, J, 3], R [N, 3, 3], scale [N], t [N, 3]) f64 on the device, Z = scale * B R + t."""
+    require_cuda(A, B)
+    if A.dim() != 3 or A.shape[2] != 3 or A.shape != B.shape or A.shape[0] < 1 or A.shape[1] < 1:
+        raise ValueError('procrustes: two [N, J, 3] tensors of one shape expected, got %s and %s'
+                         % (tuple(A.shape), tuple(B.shape)))
+    if isinstance(reflection, str) and reflection != 'best' or reflection not in _REFLECTION:
+        raise ValueError("procrustes: reflection must be 'best', True or False, got %r" % (reflection,))
+    A, B = _f64(A), _f64(B)
+    n, j, _ = A.shape
+    dev = A.device
+    d = torch.empty((n,), dtype=torch.float64, device=dev)
+    Z = torch.empty((n, j, 3), dtype=torch.float64, device=dev)
+    R = torch.empty((n, 3, 3), dtype=torch.float64, device=dev)
+    scale = torch.empty((n,), dtype=torch.float64, device=dev)
+    t = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    call('posu_procrustes', ptr(A), ptr(B), n, j, int(bool(scaling)), _REFLECTION[reflection], ptr(d), ptr(Z), ptr(R),
+         ptr(scale), ptr(t), stream_of(dev))
+    return d, Z, R, scale, t
+
+
+def pose3d_errors(X, gt, R, T, procrustes=False, return_aligned=False):
+    """error_computing_3d for a batch (posu_pose3d_errors): X [G, J, 3] world frame, gt [G, V, J, 3] camera
+    frames, R [G, V, 3, 3], T [G, V, 3] (or [G, V, 3, 1]) cuda -> err [G, V, J] f64 (with return_aligned
+    also pred [G, V, J, 3], Procrustes-aligned onto gt when procrustes is set)."""
+    require_cuda(X, gt, R, T)
+    if gt.dim() != 4 or gt.shape[3] != 3 or gt.shape[0] < 1 or gt.shape[1] < 1 or gt.shape[2] < 1:
+        raise ValueError('pose3d_errors: gt must be [G, V, J, 3], got %s' % (tuple(gt.shape),))
+    g, v, j, _ = gt.shape
+    if tuple(X.shape) != (g, j, 3) or tuple(R.shape) != (g, v, 3, 3) or T.numel() != g * v * 3:
+        raise ValueError('pose3d_errors: X [G, J, 3], R [G, V, 3, 3], T [G, V, 3] expected for gt %s; got %s, %s, %s'
+                         % (tuple(gt.shape), tuple(X.shape), tuple(R.shape), tuple(T.shape)))
+    X, gt, R, T = _f64(X), _f64(gt), _f64(R), _f64(T.reshape(g, v, 3))
+    dev = gt.device
+    err = torch.empty((g, v, j), dtype=torch.float64, device=dev)
+    aligned = torch.empty((g, v, j, 3), dtype=torch.float64, device=dev) if return_aligned else None
+    call('posu_pose3d_errors', ptr(X), ptr(gt), ptr(R), ptr(T), g, v, j, int(bool(procrustes)), ptr(err), ptr(aligned),
+         stream_of(dev))
+    return (err, aligned) if return_aligned else err
+
+
+def limb_break(X, parent, limb, thres=0.4, return_worst=False):
+    """break_limb_length for a batch (posu_limb_break): X [G, J, 3], parent [J] (-1 at the root), limb [G, J]
+    or one shared [J] by child joint, all cuda -> flag [G] uint8 (with return_worst also the largest
+    offset / limb [G] f64)."""
+    require_cuda(X, parent, limb)
+    if X.dim() != 3 or X.shape[2] != 3 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError('limb_break: X must be [G, J, 3], got %s' % (tuple(X.shape),))
+    g, j, _ = X.shape
+    if tuple(parent.shape) != (j,) or tuple(limb.shape) not in ((j,), (g, j)):
+        raise ValueError('limb_break: parent [J] and limb [J] or [G, J] expected for X %s; got %s, %s'
+                         % (tuple(X.shape), tuple(parent.shape), tuple(limb.shape)))
+    X, limb = _f64(X), _f64(limb)
+    parent = parent.to(torch.int32).contiguous()
+    dev = X.device
+    flag = torch.empty((g,), dtype=torch.uint8, device=dev)
+    worst = torch.empty((g,), dtype=torch.float64, device=dev) if return_worst else None
+    call('posu_limb_break', ptr(X), ptr(parent), ptr(limb), j if limb.dim() == 2 else 0, g, j, float(thres), ptr(flag),
+         ptr(worst), stream_of(dev))
+    return (flag, worst) if return_worst else flag
