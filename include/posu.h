@@ -78,7 +78,8 @@ const char* posu_last_error(void);
  * posu_adam_step_dev, posu_loss_scale_update) are additive to 16: new symbols only, the revision
  * does not move; so are the heatmap mutual-information ones and the training loop's metrics
  * (posu_pck_accuracy, posu_grad_row_norms, posu_meters_update and their workspace queries) and the
- * 3-D evaluation protocol (posu_procrustes, posu_pose3d_errors, posu_limb_break).  The
+ * 3-D evaluation protocol (posu_procrustes, posu_pose3d_errors, posu_limb_break) and the
+ * pseudo-label round (posu_pseudo_label_workspace, posu_pseudo_label_sweep, posu_pckh_counts).  The
  * ctypes binding refuses a library of another revision. */
 int posu_abi_version(void);
 
@@ -931,6 +932,48 @@ int posu_pose3d_errors(const double* X, const double* gt, const double* R, const
  *           ratios are passed over; 0 without edges). */
 int posu_limb_break(const double* X, const int* parent, const double* limb, int limb_stride, int G, int J,
                     double thres, unsigned char* flag, double* worst, void* stream);
+
+/* ------------------------------------------------------ pseudo-label round */
+/* The loop of run/test/test_pseudo_label.py:193-259 for a sweep of T (1..8) confidence thresholds in
+ * one launch, one thread per (group, joint).  The pair triangulations of ransac (triangulate.py:142-155)
+ * and their reprojection errors do not depend on the confidence threshold: they are solved once and
+ * every threshold reuses them.  Per threshold t:
+ *   stage 0  conf > thre[t], compared in f32 as numpy compares an f32 array with a Python float
+ *            (test_pseudo_label.py:194);
+ *   stage 1  ransac (triangulate.py:102-165) on the stage-0 mask: posu_ransac_inliers' result;
+ *   stage 2  reproject_poses (triangulate.py:169-213) on the stage-1 mask when use_ransac is set, on
+ *            the stage-0 mask otherwise: posu_reproject's result.  The n-view solve is repeated only
+ *            when the mask differs from the one last solved.
+ *   M: [G, V, 3, 4] f64;  intr: [G, V, 9] f64;  xy: [G, V, J, 2] f64;  conf: [G, V, J] f32;
+ *   thre: HOST array of T floats;  2 <= V <= 4;  min_inliers >= 1;
+ *   vis_out:  [T, 3, G, V, J] uint8, the three stages' masks;
+ *   proj_out: [T, G, V, J, 2] f64, stage 2's projections (zeros where fewer than 2 views were on).
+ * G == 0 returns POSU_OK without a launch.
+ *
+ * posu_pseudo_label_workspace answers on the host: the bytes of one round's device results laid out as
+ * proj_out, then the posu_pckh_counts table of the T * 3 sets ([T * 3, 2J + V + 1] int32, padded to a
+ * multiple of 8 bytes), then vis_out -- one allocation, one read-back.  -1 outside 1 <= T <= 8,
+ * 2 <= V <= 4, J > 0, G >= 0. */
+long long posu_pseudo_label_workspace(int T, int G, int V, int J);
+int posu_pseudo_label_sweep(const double* M, const double* intr, const double* xy, const float* conf,
+                            const float* thre, int T, int G, int V, int J, int undistort,
+                            double reproj_thre, int min_inliers, int use_ransac, unsigned char* vis_out,
+                            double* proj_out, void* stream);
+
+/* The reductions behind my_eval (test_pseudo_label.py:89-105), np.sum(joints_vis) (:196) and the
+ * Joints@k lines (:197-205) for B (1..32) label sets of N = G * V frames (group-major) at once.
+ *   vis:  [B, N, J] uint8;  gt: NULL or [N, J, 2] f64;  head: [N] f64 (the frames' head sizes);
+ *   pred: [N, J, 2] f64, the predictions shared by the sets;  pred_sets: NULL or [S, N, J, 2] f64;
+ *   set_pred: NULL (every set reads pred) or a HOST array of B ints: set b reads pred when
+ *             set_pred[b] < 0 and pred_sets[set_pred[b]] otherwise;
+ *   counts: [B, 2J + V + 1] int32, zeroed here on the stream: [j] frames with joint j visible and
+ *           sqrt((gt - pred)^2 summed over x, y) / head <= threshold (f64, :96-98), [J + j] frames with
+ *           joint j visible, [2J + k] the (group, joint)s visible in exactly k of the V (1..8) views.
+ * gt == NULL leaves the detection counts zero (loop training without ground truth).  Integer
+ * atomics: the result does not depend on the order.  N == 0 zeroes counts and launches nothing. */
+int posu_pckh_counts(const double* pred, const double* pred_sets, const int* set_pred,
+                     const unsigned char* vis, const double* gt, const double* head, int B, int N, int J,
+                     int V, double threshold, int* counts, void* stream);
 
 #ifdef __cplusplus
 }

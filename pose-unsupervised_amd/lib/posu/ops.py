@@ -1053,3 +1053,87 @@ def limb_break(X, parent, limb, thres=0.4, return_worst=False):
     call('posu_limb_break', ptr(X), ptr(parent), ptr(limb), j if limb.dim() == 2 else 0, g, j, float(thres), ptr(flag),
          ptr(worst), stream_of(dev))
     return (flag, worst) if return_worst else flag
+
+
+# ----------------------------------------------------------- pseudo-label round
+def pseudo_label_workspace(t, g, v, j):
+    """Bytes of one round's device results (posu_pseudo_label_workspace: projections, counts, masks); raises
+    outside 1 <= T <= 8, 2 <= V <= 4, J > 0, G >= 0."""
+    n = nat.load().posu_pseudo_label_workspace(int(t), int(g), int(v), int(j))
+    if n < 0:
+        raise ValueError('pseudo_label_workspace: 1 <= T <= 8, 2 <= V <= 4, J > 0, G >= 0 expected, got T=%d G=%d '
+                         'V=%d J=%d' % (t, g, v, j))
+    return n
+
+
+def pseudo_label_sweep(M, intr, xy, conf, thresholds, reproj_thre=20.0, min_inliers=2, use_ransac=True,
+                       undistort=True, vis_out=None, proj_out=None):
+    """The threshold / RANSAC / reprojection stages of test_pseudo_label.py's loop for every threshold in one
+    launch (posu_pseudo_label_sweep): M [G, V, 3, 4] f64, intr [G, V, 9] f64, xy [G, V, J, 2], conf [G, V, J] f32,
+    all cuda; thresholds: up to 8 numbers, compared in f32 -> (masks [T, 3, G, V, J] uint8 of the stages
+    threshold / RANSAC / reprojection, proj [T, G, V, J, 2] f64)."""
+    require_cuda(M, intr, xy, conf, vis_out, proj_out)
+    if xy.dim() != 4 or xy.shape[3] != 2:
+        raise ValueError('pseudo_label_sweep: xy must be [G, V, J, 2], got %s' % (tuple(xy.shape),))
+    g, v, j, _ = xy.shape
+    if tuple(conf.shape) != (g, v, j) or M.numel() != g * v * 12 or intr.numel() != g * v * 9:
+        raise ValueError('pseudo_label_sweep: conf [G, V, J], M [G, V, 3, 4], intr [G, V, 9] expected for xy %s; '
+                         'got %s, %s, %s' % (tuple(xy.shape), tuple(conf.shape), tuple(M.shape), tuple(intr.shape)))
+    if conf.dtype != torch.float32:
+        raise TypeError('pseudo_label_sweep: conf must be float32 (the thresholds are compared in f32), got %s'
+                        % conf.dtype)
+    thre = np.ascontiguousarray(thresholds, dtype=np.float32).reshape(-1)
+    t = int(thre.size)
+    dev = xy.device
+    xy, conf = _f64(xy), conf.detach().contiguous()
+    if vis_out is None:
+        vis_out = torch.empty((t, 3, g, v, j), dtype=torch.uint8, device=dev)
+    if proj_out is None:
+        proj_out = torch.empty((t, g, v, j, 2), dtype=torch.float64, device=dev)
+    if (vis_out.dtype, proj_out.dtype) != (torch.uint8, torch.float64) or vis_out.numel() != t * 3 * g * v * j \
+            or proj_out.numel() != t * g * v * j * 2 or not (vis_out.is_contiguous() and proj_out.is_contiguous()):
+        raise ValueError('pseudo_label_sweep: vis_out [T, 3, G, V, J] uint8 and proj_out [T, G, V, J, 2] f64, '
+                         'contiguous, expected')
+    nat.call('posu_pseudo_label_sweep', ptr(_f64(M)), ptr(_f64(intr)), ptr(xy), ptr(conf), _host(thre), t, g, v, j,
+         int(bool(undistort)), float(reproj_thre), int(min_inliers), int(bool(use_ransac)), ptr(vis_out),
+         ptr(proj_out), stream_of(dev))
+    return vis_out.view(t, 3, g, v, j), proj_out.view(t, g, v, j, 2)
+
+
+def pckh_counts(pred, vis, gt, head, nviews=1, threshold=0.5, pred_sets=None, set_pred=None, out=None):
+    """Integer counts behind my_eval and the Joints@k lines for B label sets (posu_pckh_counts): vis [B, N, J]
+    (non-zero = visible), pred [N, J, 2] shared by the sets, gt [N, J, 2] or None, head [N] (or [N, 1]), all
+    cuda; pred_sets [S, N, J, 2] with set_pred (B ints: -1 = pred, s = pred_sets[s]) gives sets predictions of
+    their own -> counts [B, 2J + nviews + 1] int32: detected-and-visible per joint, visible per joint, and the
+    histogram of visible views per (group, joint) for N = G * nviews group-major frames."""
+    require_cuda(pred, vis, gt, head, pred_sets, out)
+    if vis.dim() != 3:
+        raise ValueError('pckh_counts: vis must be [B, N, J], got %s' % (tuple(vis.shape),))
+    b, n, j = vis.shape
+    if gt is not None and (pred is None or head is None or tuple(gt.shape) != (n, j, 2) or head.numel() != n):
+        raise ValueError('pckh_counts: gt [N, J, 2] needs pred and head [N]')
+    if pred is not None and tuple(pred.shape) != (n, j, 2):
+        raise ValueError('pckh_counts: pred must be [N, J, 2] for vis %s, got %s' % (tuple(vis.shape), tuple(pred.shape)))
+    sel = None
+    if set_pred is not None:
+        sel = np.ascontiguousarray(set_pred, dtype=np.int32).reshape(-1)
+        nsets = 0 if pred_sets is None else pred_sets.numel() // max(n * j * 2, 1)
+        if sel.size != b or (sel >= nsets).any():
+            raise ValueError('pckh_counts: set_pred needs B entries below the number of pred_sets')
+        if pred_sets is not None and (pred_sets.dtype != torch.float64 or not pred_sets.is_contiguous()):
+            raise ValueError('pckh_counts: pred_sets must be contiguous float64')
+    dev = vis.device
+    vis = vis.detach()
+    if vis.dtype != torch.uint8:
+        vis = vis.ne(0).to(torch.uint8)
+    vis = vis.contiguous()
+    w = 2 * j + int(nviews) + 1
+    if out is None:
+        out = torch.empty((b, w), dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or out.numel() != b * w or not out.is_contiguous():
+        raise ValueError('pckh_counts: out must be contiguous int32 [B, 2J + nviews + 1]')
+    nat.call('posu_pckh_counts', ptr(None if pred is None else _f64(pred)), ptr(pred_sets),
+         None if sel is None else _host(sel), ptr(vis), ptr(None if gt is None else _f64(gt)),
+         ptr(None if head is None else _f64(head.reshape(-1))), b, n, j, int(nviews), float(threshold), ptr(out),
+         stream_of(dev))
+    return out.view(b, w)
