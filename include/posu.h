@@ -79,7 +79,8 @@ const char* posu_last_error(void);
  * does not move; so are the heatmap mutual-information ones and the training loop's metrics
  * (posu_pck_accuracy, posu_grad_row_norms, posu_meters_update and their workspace queries) and the
  * 3-D evaluation protocol (posu_procrustes, posu_pose3d_errors, posu_limb_break) and the
- * pseudo-label round (posu_pseudo_label_workspace, posu_pseudo_label_sweep, posu_pckh_counts).  The
+ * pseudo-label round (posu_pseudo_label_workspace, posu_pseudo_label_sweep, posu_pckh_counts) and the
+ * training sample (posu_sample_workspace, posu_sample_images, posu_sample_joints_targets).  The
  * ctypes binding refuses a library of another revision. */
 int posu_abi_version(void);
 
@@ -468,6 +469,65 @@ int posu_gaussian_targets(const float* joints, const float* vis, int N, int J, i
                           int image_h, int hm_w, int hm_h, double sigma,
                           const unsigned char* zero_weight, float* target, float* weight,
                           void* stream);
+
+/* The training sample of JointsDatasetCompatible.__getitem__ (lib/dataset/joints_dataset_compatible.py
+ * :111-201) for N records per enqueue, in two calls: the images and the labels.
+ *
+ * One record's colour jitter: torchvision ColorJitter (joints_dataset_compatible.py:67-71) with its drawn
+ * parameters.  order: the four operations by torchvision's fn_id (0 brightness, 1 contrast, 2 saturation,
+ * 3 hue) in the order they run; any other value is skipped.  hue_shift: trunc(hue * 255) mod 256 (adjust_hue's
+ * uint8 add).  active = 0: the record is not jittered. */
+typedef struct posu_jitter {
+  float brightness, contrast, saturation;
+  unsigned char order[4];
+  unsigned char hue_shift;
+  unsigned char active;
+  unsigned char reserved[2];
+} posu_jitter;
+
+/* Bytes of posu_sample_images' workspace for N records (one 64-bit sum each); -1 for N < 0. */
+long long posu_sample_workspace(int N);
+
+/* The input crops: per record
+ *   flip    flip[n] != 0: data_numpy[:, ::-1, :] before the warp (:156) -- a source tap at column tx reads
+ *           column W - 1 - tx, the border test stays on tx (exact; the matrix is not touched);
+ *   warp    posu_crop_warp's arithmetic (:162-165);
+ *   jitter  on the uint8 RGB triple (:168-172; bgr != 0: the source is cv2's BGR, reversed before and after),
+ *           PIL's arithmetic: ImageEnhance's blends d + f * (x - d) in f32 (truncated for 0 <= f <= 1, else
+ *           clipped to [0, 255] and truncated) against black (brightness), the pixel's own
+ *           L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 (saturation) and one grey per image,
+ *           int(mean(L) + 0.5) (contrast); the hue as Convert.c's RGB -> HSV, H += hue_shift mod 256,
+ *           HSV -> RGB, done for a shift of 0 too (the round trip is lossy);
+ *   output  mode 0: uint8 [N, dh, dw, 3]; mode 1: ToTensor + Normalize (:173), f32 [N, 3, dh, dw].
+ * src, src_off, src_hw, M, mode, mean, std: as posu_crop_warp's, C == 3.  flip: NULL or [N] uint8;
+ * jitter: NULL or [N] records (device).  contrast != 0 when some active record has a contrast step: a first
+ * pass then recomputes the warp and the operations before that step and sums L exactly (integers, one
+ * 64-bit atomic per block) into the workspace, which is zeroed on the stream first; without it the
+ * contrast step must not occur.  workspace: posu_sample_workspace(N) bytes, needed with jitter records;
+ * after the call it holds the records' L sums ([N] uint64, 0 for records without a contrast step).
+ * Nothing is allocated and nothing synchronises: the call can be captured. */
+int posu_sample_images(const unsigned char* src, const long long* src_off, const int* src_hw, int C,
+                       const double* M, const unsigned char* flip, const posu_jitter* jitter, int contrast,
+                       int bgr, int N, int dh, int dw, int mode, const float* mean, const float* std,
+                       void* workspace, long long workspace_bytes, void* out, void* stream);
+
+/* The labels, in one launch and in f64 where the reference is f64: per record
+ *   flip    fliplr_joints (lib/utils/transforms.py:50-64): x = W - x - 1 with W = src_hw[2n + 1], the pair
+ *           swap of joints and vis (joint j reads joint perm[j]), joints * vis;
+ *   affine  [x, y, 1] . trans^T for the joints with vis[:, 0] > 0 (:175-177, transforms.py:112-120).  numpy
+ *           hands the product to BLAS, whose kernels fuse one multiply-add; its two forms are reproduced:
+ *           fma(y, t1, x * t0) + t2 with two or more visible joints, fma(x, t0, y * t1) + t2 with one;
+ *   target  generate_heatmap (:207-253): mu = int(joint / stride + 0.5) in f64, the Gaussian in f32 with
+ *           numpy's own float32 exp (its AVX2 / AVX512F kernel: faithful, not correctly rounded) restated.
+ * joints, vis: [N, J, 2] f64 (vis: the first two columns of joints_vis); flip: NULL or [N] uint8 (then
+ * src_hw [N][2] int32 and perm [J] int32 are needed); M: [N][2][3] f64; zero_weight: NULL or [N] uint8.
+ * joints_out, vis_out: [N, J, 2] f64 (meta's joints_2d_transformed / joints_vis); target [N, J, hm_h, hm_w]
+ * f32; weight [N, J] f32. */
+int posu_sample_joints_targets(const double* joints, const double* vis, const unsigned char* flip,
+                               const int* src_hw, const int* perm, const double* M,
+                               const unsigned char* zero_weight, int N, int J, int image_w, int image_h,
+                               int hm_w, int hm_h, double sigma, double* joints_out, double* vis_out,
+                               float* target, float* weight, void* stream);
 /* Sum-normalised integral coordinates (run/test/test_integral.py:63-70):
  * out[n][j] = (sum x h, sum y h) / sum h  over hm [N, J, H, W] f32 -> [N, J, 2] f32. */
 int posu_integral2d_fwd(const float* hm, int N, int J, int H, int W, float* out, void* stream);

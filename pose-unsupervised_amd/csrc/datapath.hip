@@ -8,6 +8,7 @@
 //                      lib/dataset/joints_dataset_compatible.py:161-164) for a whole batch,
 //                      optionally fused with ToTensor + Normalize, one thread per output pixel.
 #include "posu_common.h"
+#include "warp_common.h"
 
 namespace posu {
 namespace {
@@ -75,14 +76,7 @@ __global__ __launch_bounds__(256) void integral_kernel(const float* __restrict__
   }
 }
 
-// OpenCV 3.4's warpAffine (imgwarp.cpp: WarpAffineInvoker + remapBilinear, 8-bit) restated:
-// the src -> dst matrix inverted in double; source coordinates in 1/1024-px fixed point
-// (cvRound = round half to even) with the row term and the column term rounded separately,
-// reduced to 1/32 px; the 4 taps weighted by the exact-integer bilinear table (sum 32768);
-// (sum + 2^14) >> 15.  Border: constant 0 -- a pixel whose 2x2 footprint misses the image is 0,
-// a partly covered one takes 0 for the missing taps.  No FMA contraction anywhere: every
-// double is rounded like OpenCV's separate multiplies and adds.
-#pragma clang fp contract(off)
+// The crop warp (warp_common.h has OpenCV's arithmetic), one thread per output pixel.
 __global__ __launch_bounds__(256) void crop_warp_kernel(const unsigned char* __restrict__ src,
                                                         const long long* __restrict__ src_off,
                                                         const int* __restrict__ src_hw, int C,
@@ -95,53 +89,20 @@ __global__ __launch_bounds__(256) void crop_warp_kernel(const unsigned char* __r
     const long long r = i / dw;
     const int y = static_cast<int>(r % dh);
     const int n = static_cast<int>(r / dh);
-    const double* Mi = Mall + 6 * n;
-    double m0 = Mi[0], m1 = Mi[1], m2 = Mi[2], m3 = Mi[3], m4 = Mi[4], m5 = Mi[5];
-    double D = m0 * m4 - m1 * m3;
-    D = D != 0.0 ? 1.0 / D : 0.0;
-    const double a11 = m4 * D, a22 = m0 * D;
-    m0 = a11;
-    m1 *= -D;
-    m3 *= -D;
-    m4 = a22;
-    const double b1 = -m0 * m2 - m1 * m5;
-    const double b2 = -m3 * m2 - m4 * m5;
-    m2 = b1;
-    m5 = b2;
-    const int adelta = static_cast<int>(rint(m0 * x * 1024.0));
-    const int bdelta = static_cast<int>(rint(m3 * x * 1024.0));
-    const int X0 = static_cast<int>(rint((m1 * y + m2) * 1024.0)) + 16;
-    const int Y0 = static_cast<int>(rint((m4 * y + m5) * 1024.0)) + 16;
-    const int X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
-    const int sx = min(max(X >> 5, -32768), 32767), sy = min(max(Y >> 5, -32768), 32767);
-    const int fx = X & 31, fy = Y & 31;
-    const int w[4] = {(32 - fy) * (32 - fx) * 32, (32 - fy) * fx * 32, fy * (32 - fx) * 32, fy * fx * 32};
     const int H = src_hw[2 * n], W = src_hw[2 * n + 1];
+    const WarpTaps t = warp_taps(Mall + 6 * n, x, y, H, W);
     const unsigned char* S = src + src_off[n];
-    const bool outside = sx >= W || sx + 1 < 0 || sy >= H || sy + 1 < 0;
     for (int c = 0; c < C; ++c) {
-      int v = 0;
-      if (!outside) {
-        int acc = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int tx = sx + (k & 1), ty = sy + (k >> 1);
-          if (tx >= 0 && tx < W && ty >= 0 && ty < H)
-            acc += static_cast<int>(S[(static_cast<long long>(ty) * W + tx) * C + c]) * w[k];
-        }
-        v = (acc + (1 << 14)) >> 15;
-        v = v < 0 ? 0 : (v > 255 ? 255 : v);
-      }
+      const int v = warp_channel(S, H, W, C, c, t, false);
       if (mode == 0) {
         static_cast<unsigned char*>(out)[(r * dw + x) * C + c] = static_cast<unsigned char>(v);
       } else {
-        const float t = static_cast<float>(v) / 255.f;
-        static_cast<float*>(out)[((static_cast<long long>(n) * C + c) * dh + y) * dw + x] = (t - mean[c]) / stdv[c];
+        const float t01 = static_cast<float>(v) / 255.f;
+        static_cast<float*>(out)[((static_cast<long long>(n) * C + c) * dh + y) * dw + x] = (t01 - mean[c]) / stdv[c];
       }
     }
   }
 }
-#pragma clang fp contract(on)
 
 inline int grid_for(long long total) {
   long long g = (total + 255) / 256;

@@ -134,6 +134,10 @@ _SIGNATURES = {
     'posu_pseudo_label_workspace': [_i, _i, _i, _i],
     'posu_pseudo_label_sweep': [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _d, _i, _i, _p, _p, _p],
     'posu_pckh_counts': [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _d, _p, _p],
+    # training sample (additive to ABI 16)
+    'posu_sample_workspace': [_i],
+    'posu_sample_images': [_p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _ll, _p, _p],
+    'posu_sample_joints_targets': [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p, _p],
 }
 _RESTYPES = {'posu_last_error': ctypes.c_char_p, 'posu_conv2d_wgrad_workspace': ctypes.c_longlong,
              'posu_pack_job_blocks': ctypes.c_longlong,
@@ -142,7 +146,7 @@ _RESTYPES = {'posu_last_error': ctypes.c_char_p, 'posu_conv2d_wgrad_workspace': 
              'posu_grad_stats_workspace': ctypes.c_longlong, 'posu_heatmap_mi_workspace': ctypes.c_longlong,
              'posu_heatmap_dparams_floats': ctypes.c_longlong, 'posu_pair_mi_workspace': ctypes.c_longlong,
              'posu_pck_accuracy_workspace': ctypes.c_longlong, 'posu_grad_row_norms_workspace': ctypes.c_longlong,
-             'posu_pseudo_label_workspace': ctypes.c_longlong}
+             'posu_pseudo_label_workspace': ctypes.c_longlong, 'posu_sample_workspace': ctypes.c_longlong}
 
 
 def library_path():

@@ -68,6 +68,16 @@ def affine_transform(pt, t):
     return np.dot(pt, t.T).squeeze()
 
 
+def fliplr_joints(joints, joints_vis, width, matched_parts):
+    """Reference transforms.py:50-64: mirror x, swap the left / right pairs of joints and joints_vis (both
+    in place, like the reference) and return (joints * joints_vis, joints_vis)."""
+    joints[:, 0] = width - joints[:, 0] - 1
+    for a, b in matched_parts:
+        joints[a, :], joints[b, :] = joints[b, :], joints[a, :].copy()
+        joints_vis[a, :], joints_vis[b, :] = joints_vis[b, :], joints_vis[a, :].copy()
+    return joints * joints_vis, joints_vis
+
+
 def transform_preds(coords, center, scale, output_size):
     target = np.zeros(coords.shape)
     trans = get_affine_transform(center, scale, 0, output_size, inv=1)
