@@ -171,20 +171,12 @@ __global__ __launch_bounds__(64) void triangulate_kernel(const double* __restric
     if constexpr (FOLD) {
       if (on) {
         double a0[4], a1[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          a0[c] = u * M[8 + c] - M[c];
-          a1[c] = vv * M[8 + c] - M[4 + c];
-        }
+        dlt_rows(M, u, vv, true, a0, a1);
         givens_fold(A, a0);
         givens_fold(A, a1);
       }
     } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        A[2 * v][c] = on ? u * M[8 + c] - M[c] : 0.0;
-        A[2 * v + 1][c] = on ? vv * M[8 + c] - M[4 + c] : 0.0;
-      }
+      dlt_rows(M, u, vv, on, A[2 * v], A[2 * v + 1]);
     }
   }
   double* out = X + static_cast<size_t>(t) * 3;
@@ -290,57 +282,21 @@ __global__ __launch_bounds__(64) void ransac_kernel(const double* __restrict__ M
   const int g = t / J, k = t - g * J;
   ViewPts p;
   load_views(Mall, intr, xy, vis, g, k, V, J, undistort, p);
-  int best_mask = 0, best_n = 0;
-  double best_err = 10000.0;
+  BestPair best;
   if (p.nvis >= 2) {
-    // itertools.combinations over the visible views, in view order (loops unrolled: the view
-    // indices are compile-time, so p's arrays stay in registers -- a run-time index put them in
-    // 144 B of scratch)
+    // itertools.combinations over the visible views, in view order (unrolled: compile-time indices)
 #pragma unroll
     for (int a = 0; a < kPairViews; ++a) {
 #pragma unroll
       for (int b = a + 1; b < kPairViews; ++b) {
         if (!p.on[a] || !p.on[b]) continue;
-        double A[4][4];
-        const int pv[2] = {a, b};
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          const double* M = Mall + (static_cast<size_t>(g) * V + pv[r]) * 12;
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            A[2 * r][c] = p.und[pv[r]][0] * M[8 + c] - M[c];
-            A[2 * r + 1][c] = p.und[pv[r]][1] * M[8 + c] - M[4 + c];
-          }
-        }
-        double X[3];
-        dlt_point<4>(A, X);
-        int mask = 0, n = 0;
-        double err = 0.0;
-#pragma unroll
-        for (int v = 0; v < kPairViews; ++v) {
-          if (v >= V) break;
-          const size_t gv = static_cast<size_t>(g) * V + v;
-          double u, w;
-          project_px(Mall + gv * 12, intr + gv * 9, X, u, w);
-          const double du = u - p.raw[v][0], dv = w - p.raw[v][1];
-          const double e = sqrt(du * du + dv * dv);
-          if (e < thre) {
-            mask |= 1 << v;
-            ++n;
-            err += e;
-          }
-        }
-        if (n < min_inliers) continue;
-        err /= n;
-        if (n > best_n || (n == best_n && err < best_err)) {
-          best_n = n;
-          best_mask = mask;
-          best_err = err;
-        }
+        const PairScore s = score_pair(Mall, intr, p, g, V, a, b, thre);
+        if (s.n < min_inliers) continue;
+        best.offer(s.mask, s.n, s.err_sum / s.n);
       }
     }
   }
-  for (int v = 0; v < V; ++v) res_vis[(static_cast<size_t>(g) * V + v) * J + k] = (best_mask >> v) & 1;
+  for (int v = 0; v < V; ++v) res_vis[(static_cast<size_t>(g) * V + v) * J + k] = (best.mask >> v) & 1;
 }
 
 __global__ __launch_bounds__(64) void reproject_kernel(const double* __restrict__ Mall, const double* __restrict__ intr,
@@ -354,26 +310,20 @@ __global__ __launch_bounds__(64) void reproject_kernel(const double* __restrict_
   ViewPts p;
   load_views(Mall, intr, xy, vis, g, k, V, J, undistort, p);
   const bool ok = p.nvis >= 2;
-  double X[3] = {0.0, 0.0, 0.0};
-  if (ok) {
-    double A[2 * kPairViews][4];
+  int mask = 0;
+  double pj[kPairViews][2];
 #pragma unroll
-    for (int v = 0; v < kPairViews; ++v) {
-      const double* M = Mall + (static_cast<size_t>(g) * V + (v < V ? v : 0)) * 12;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        A[2 * v][c] = p.on[v] ? p.und[v][0] * M[8 + c] - M[c] : 0.0;
-        A[2 * v + 1][c] = p.on[v] ? p.und[v][1] * M[8 + c] - M[4 + c] : 0.0;
-      }
-    }
-    dlt_point<2 * kPairViews>(A, X);
+  for (int v = 0; v < kPairViews; ++v) {
+    mask |= p.on[v] << v;
+    pj[v][0] = pj[v][1] = 0.0;
   }
-  for (int v = 0; v < V; ++v) {
+  if (ok) solve_project(Mall, intr, p, g, V, mask, pj);
+#pragma unroll
+  for (int v = 0; v < kPairViews; ++v) {
+    if (v >= V) break;
     const size_t gv = static_cast<size_t>(g) * V + v;
-    double u = 0.0, w = 0.0;
-    if (ok) project_px(Mall + gv * 12, intr + gv * 9, X, u, w);
-    proj[(gv * J + k) * 2] = u;
-    proj[(gv * J + k) * 2 + 1] = w;
+    proj[(gv * J + k) * 2] = pj[v][0];
+    proj[(gv * J + k) * 2 + 1] = pj[v][1];
     res_vis[gv * J + k] = ok ? 1 : 0;
   }
 }

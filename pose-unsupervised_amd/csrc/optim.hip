@@ -181,17 +181,11 @@ struct GradLaunch {
 
 __device__ __forceinline__ bool non_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {   // butterfly: every lane ends with the same sum
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // fixed-order block sum of one double per thread (N threads, a multiple of 64); thread 0 has it
 template <int N>
 __device__ __forceinline__ double block_sum_f64(double v) {
   __shared__ double wsum[N / 64];
-  v = wave_sum_f64(v);
+  v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
   __syncthreads();
   double s = 0.0;

@@ -2,30 +2,24 @@
 // (PoseUtils.procrustes, lib/utils/pose_utils.py:61-143), the per-camera joint errors
 // (error_computing_3d, estimate.py:110-123) and the limb-length check (break_limb_length,
 // estimate.py:84-96).  Latency-bound, tiny working sets: one wave per pose, lanes stride over the
-// joints (so J may exceed 64), every sum a wave reduction over __shfl_xor; no LDS, no atomics.
+// joints (so J may exceed 64), every sum a wave reduction (posu_common.h); no LDS, no atomics.
 //
 // Procrustes follows the reference's order of operations: subtract the means, ssX / ssY and the
 // norms, divide by them, M = A0^T B0, SVD, R = V U^T, S_trace = sum s, then scale / d / Z /
-// translation (the second branch with scaling off).  The 3 x 3 SVD is a one-sided (Hestenes)
-// Jacobi in registers like dlt_point (geometry.hip): column pairs of M are rotated until mutually
-// orthogonal, the rotations accumulate in V, the column norms are the singular values and the
-// normalised columns are U.  Every matrix is indexed by compile-time constants only (a run-time
-// index would put it in scratch).  At most 30 sweeps, and the rotation test is false for NaN, so a
-// degenerate pose (all joints equal: 0 / 0) ends with NaN rows instead of spinning.  For a rank-2 M
-// (coplanar joints) the missing column of U is the cross product of the other two, where LAPACK
-// completes the basis with a sign of its choice; collinear joints (rank 1) have no defined result.
-#include "posu_common.h"
+// translation (the second branch with scaling off).  The 3 x 3 SVD is jacobi_columns
+// (geometry_common.h), the loop dlt_point runs: on return the column norms of M are the singular
+// values and the normalised columns are U.  Every matrix is indexed by compile-time constants only
+// (a run-time index would put it in scratch).  At most 30 sweeps, and the rotation test is false
+// for NaN, so a degenerate pose (all joints equal: 0 / 0) ends with NaN rows instead of spinning.
+// For a rank-2 M (coplanar joints) the missing column of U is the cross product of the other two,
+// where LAPACK completes the basis with a sign of its choice; collinear joints (rank 1) have no
+// defined result.
+#include "geometry_common.h"
 
 namespace posu {
 namespace {
 
 constexpr int kWavesPerBlock = 4;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // the rigid (or similarity) transform of one pose pair, identical in every lane of the wave
 struct Tform {
@@ -36,44 +30,12 @@ struct Tform {
   double scale, d;
 };
 
-// M = U diag(s) V^T by one-sided Jacobi on M's columns -> R = V U^T and s sorted descending
+// M = U diag(s) V^T by jacobi_columns on M's columns -> R = V U^T and s sorted descending
 // (numpy's order: s[2] is the one the forced reflection negates).  flip: 0 keep, 1 force a
 // reflection, 2 forbid one (pose_utils.py:111-119).
 __device__ __forceinline__ void rotation_from(double (&W)[3][3], int flip, double (&R)[3][3], double (&s)[3]) {
-  double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    bool rotated = false;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < 3; ++q) {
-        double alpha = 0, beta = 0, gamma = 0;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-          alpha += W[r][p] * W[r][p];
-          beta += W[r][q] * W[r][q];
-          gamma += W[r][p] * W[r][q];
-        }
-        // false for NaN: a degenerate pose stops rotating at once
-        if (gamma != 0.0 && fabs(gamma) > 1e-15 * sqrt(alpha * beta)) {
-          rotated = true;
-          const double zeta = (beta - alpha) / (2.0 * gamma);
-          const double tt = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-          const double cs = 1.0 / sqrt(1.0 + tt * tt), sn = cs * tt;
-#pragma unroll
-          for (int r = 0; r < 3; ++r) {
-            const double wp = W[r][p], wq = W[r][q];
-            W[r][p] = cs * wp - sn * wq;
-            W[r][q] = sn * wp + cs * wq;
-            const double vp = V[r][p], vq = V[r][q];
-            V[r][p] = cs * vp - sn * vq;
-            V[r][q] = sn * vp + cs * vq;
-          }
-        }
-      }
-    }
-    if (!rotated) break;
-  }
+  double V[3][3];
+  jacobi_columns<3, 3>(W, V);
   double sv[3], U[3][3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -324,12 +286,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void limb_break_kernel(
     const double rel = offset / expect;
     if (rel > w) w = rel;
   }
+  w = wave_max(w);  // never NaN: the comparison above is false for one
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    broke |= __shfl_xor(broke, o, 64);
-    const double other = __shfl_xor(w, o, 64);
-    if (other > w) w = other;
-  }
+  for (int o = 32; o > 0; o >>= 1) broke |= __shfl_xor(broke, o, 64);
   if (lane == 0) {
     flag[g] = static_cast<unsigned char>(broke);
     if (worst) worst[g] = w;

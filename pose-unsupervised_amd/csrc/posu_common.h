@@ -81,8 +81,9 @@ __device__ __forceinline__ uint32_t f2bf2(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2v));
 }
 
-// wave64 reductions
-__device__ __forceinline__ float wave_sum(float v) {
+// wave64 butterfly reductions (float, double, int, unsigned): every lane ends with the same value
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
@@ -90,6 +91,11 @@ __device__ __forceinline__ float wave_sum(float v) {
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
   return v;
 }
 

@@ -9,8 +9,9 @@
 // in registers; each threshold then costs a handful of integer tests, and the n-view DLT of the
 // reprojection stage is solved again only when its visibility mask changed.
 //
-// Arithmetic is geometry_common.h's, in the order posu_ransac_inliers / posu_reproject use it, so the
-// masks and projections of one threshold are those two entry points' results on that threshold's mask.
+// The arithmetic is shared by construction: score_pair, BestPair and solve_project (geometry_common.h)
+// are the functions posu_ransac_inliers / posu_reproject inline, so the masks and projections of one
+// threshold are those two entry points' results on that threshold's mask.
 #include "geometry_common.h"
 
 namespace posu {
@@ -53,38 +54,10 @@ __global__ __launch_bounds__(64) void sweep_kernel(const double* __restrict__ Ma
         pair_n[q] = 0;
         pair_err[q] = 0.0;
         if (b >= V) continue;
-        double A[4][4];
-        const int pv[2] = {a, b};
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          const double* M = Mall + (static_cast<size_t>(g) * V + pv[r]) * 12;
-#pragma unroll
-          for (int cc = 0; cc < 4; ++cc) {
-            A[2 * r][cc] = p.und[pv[r]][0] * M[8 + cc] - M[cc];
-            A[2 * r + 1][cc] = p.und[pv[r]][1] * M[8 + cc] - M[4 + cc];
-          }
-        }
-        double X[3];
-        dlt_point<4>(A, X);
-        int mask = 0, n = 0;
-        double err = 0.0;
-#pragma unroll
-        for (int v = 0; v < kPairViews; ++v) {
-          if (v >= V) break;
-          const size_t gv = static_cast<size_t>(g) * V + v;
-          double u, w;
-          project_px(Mall + gv * 12, intr + gv * 9, X, u, w);
-          const double du = u - p.raw[v][0], dv = w - p.raw[v][1];
-          const double e = sqrt(du * du + dv * dv);
-          if (e < reproj_thre) {
-            mask |= 1 << v;
-            ++n;
-            err += e;
-          }
-        }
-        pair_mask[q] = mask;
-        pair_n[q] = n;
-        if (n > 0) pair_err[q] = err / n;
+        const PairScore s = score_pair(Mall, intr, p, g, V, a, b, reproj_thre);
+        pair_mask[q] = s.mask;
+        pair_n[q] = s.n;
+        if (s.n > 0) pair_err[q] = s.err_sum / s.n;
       }
     }
   }
@@ -106,8 +79,7 @@ __global__ __launch_bounds__(64) void sweep_kernel(const double* __restrict__ Ma
 
     // stage 1 (triangulate.py:102-165): pairs of visible views; more inliers wins, then the
     // smaller mean error; fewer than two visible views leave zeros
-    int m1 = 0, best_n = 0;
-    double best_err = 10000.0;
+    BestPair best;
     {
       int q = 0;
 #pragma unroll
@@ -115,40 +87,18 @@ __global__ __launch_bounds__(64) void sweep_kernel(const double* __restrict__ Ma
 #pragma unroll
         for (int b = a + 1; b < kPairViews; ++b, ++q) {
           if (!((m0 >> a) & 1) || !((m0 >> b) & 1)) continue;
-          const int n = pair_n[q];
-          if (n < min_inliers) continue;
-          if (n > best_n || (n == best_n && pair_err[q] < best_err)) {
-            best_n = n;
-            m1 = pair_mask[q];
-            best_err = pair_err[q];
-          }
+          if (pair_n[q] < min_inliers) continue;
+          best.offer(pair_mask[q], pair_n[q], pair_err[q]);
         }
       }
     }
+    const int m1 = best.mask;
 
     // stage 2 (triangulate.py:169-213) on the stage-1 mask with RANSAC, else on the stage-0 mask
     const int src = use_ransac ? m1 : m0;
     const bool ok = __popc(src) >= 2;
     if (ok && src != solved) {
-      double A[2 * kPairViews][4];
-#pragma unroll
-      for (int v = 0; v < kPairViews; ++v) {
-        const double* M = Mall + (static_cast<size_t>(g) * V + (v < V ? v : 0)) * 12;
-        const bool on = (src >> v) & 1;
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc) {
-          A[2 * v][cc] = on ? p.und[v][0] * M[8 + cc] - M[cc] : 0.0;
-          A[2 * v + 1][cc] = on ? p.und[v][1] * M[8 + cc] - M[4 + cc] : 0.0;
-        }
-      }
-      double X[3];
-      dlt_point<2 * kPairViews>(A, X);
-#pragma unroll
-      for (int v = 0; v < kPairViews; ++v) {
-        if (v >= V) break;
-        const size_t gv = static_cast<size_t>(g) * V + v;
-        project_px(Mall + gv * 12, intr + gv * 9, X, pj[v][0], pj[v][1]);
-      }
+      solve_project(Mall, intr, p, g, V, src, pj);
       solved = src;
     }
     const int m2 = ok ? all : 0;
@@ -175,12 +125,6 @@ constexpr int kMaxCountViews = 8;
 struct SetPred {
   int v[kMaxSets];
 };
-
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // One wave per (64 groups, label set): lane = group, joints in a loop.  Per joint the lanes' counts
 // are added across the wave and lane 0 issues one atomicAdd per non-zero counter; the histogram of
@@ -220,8 +164,8 @@ __global__ __launch_bounds__(64) void pckh_counts_kernel(const double* __restric
 #pragma unroll
       for (int i = 0; i <= kMaxCountViews; ++i) hist[i] += nv == i;
     }
-    nd = wave_sum_int(nd);
-    nv = wave_sum_int(nv);
+    nd = wave_sum(nd);
+    nv = wave_sum(nv);
     if (threadIdx.x == 0) {
       if (nd) atomicAdd(out + j, nd);
       if (nv) atomicAdd(out + J + j, nv);
@@ -229,7 +173,7 @@ __global__ __launch_bounds__(64) void pckh_counts_kernel(const double* __restric
   }
 #pragma unroll
   for (int i = 0; i <= kMaxCountViews; ++i) {
-    const int h = wave_sum_int(hist[i]);
+    const int h = wave_sum(hist[i]);
     if (threadIdx.x == 0 && i <= V && h) atomicAdd(out + 2 * J + i, h);
   }
 }

@@ -109,8 +109,7 @@ __device__ __forceinline__ float numpy_expf(float x) {
 
 // sum over the block's 256 threads (4 waves), valid in thread 0
 __device__ __forceinline__ unsigned block_sum_u32(unsigned v, unsigned* lds) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
   __syncthreads();
   return lds[0] + lds[1] + lds[2] + lds[3];

@@ -116,12 +116,6 @@ __global__ __launch_bounds__(64) void pck_step_kernel(const double* __restrict__
 }
 
 // ---------------------------------------------------------------- gradient row norms
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // one 256-thread block per (view, row): sum |g| (p = 1) or g^2 (p = 2) in f64, thread t over the
 // elements t, t + 256, .. (groups of four with 16-B loads), lanes then waves in a fixed order
 template <int P>
@@ -146,7 +140,7 @@ __global__ __launch_bounds__(256) void row_norm_kernel(ViewGrads grads, int N, l
     for (long long i = threadIdx.x; i < L; i += 256) s += term(g[i]);
   }
   __shared__ double part[4];
-  s = wave_sum_f64(s);
+  s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -79,6 +79,86 @@ def test_procrustes_against_the_golden_and_its_invariants(golden, cuda, J):
     print('procrustes J=%d: worst Z / gate %.3f, d / gate %.3f, rotation %.2e' % (J, worst_z, worst_d, worst_r))
 
 
+def _restatement_err(A, B, scaling, reflection, ref):
+    """The numpy restatement's distance from the 50-digit evaluation of the same formulas (mp_procrustes of
+    tests/golden/make_pose3d_golden.py, the golden's yardstick; mpmath comes with torch's sympy) for Z, d and
+    t: the ref_err of the gates."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden'))
+    import make_pose3d_golden as mk
+    md, mZ, _, _, mt = mk.mp_procrustes(A, B, scaling, reflection)
+    return mk._dist(mk._flat(mZ), ref[1]), float(abs(mk.mp.mpf(float(ref[0])) - md)), mk._dist(mk._flat(mt), ref[4])
+
+
+def _numpy_references(A, B, scaling, reflection, rank2):
+    """rs.procrustes, and at rank 2 with reflection 'best' also the same numpy SVD with the third column of U
+    negated: LAPACK completes that column with a sign of its choice, the kernel with a cross product, and with
+    'best' nothing fixes the sign afterwards (a forced reflection does, through the determinant)."""
+    refs = [rs.procrustes(A, B, scaling, reflection)]
+    if rank2 and reflection == 'best':
+        M, stats = rs._normalise(A, B)
+        U, s, Vt = np.linalg.svd(M)
+        U[:, 2] = -U[:, 2]
+        refs.append(rs._finish(A, B, s, U, Vt.T, scaling, reflection, stats))
+    return refs
+
+
+@pytest.mark.parametrize('J', [3, 65])
+def test_procrustes_five_poses_against_the_numpy_restatement(cuda, J):
+    """N = 5 leaves three waves of the second block idle; J = 3 is the smallest J with a rank-2 M (three
+    centred points span a plane), J = 65 wraps the lane stride once.  Against rs.procrustes (numpy's SVD) at
+    the gates of the golden test: 8 * max(ref_err, ulp of the largest coordinate) for Z and for t, each with
+    its own ref_err, 8 * max(ref_err_d, 2.2e-16) for d, 1e-13 for the rotation, 1e-14 for the scale, and the
+    kernel's own Z = scale * B R + t at the Z gate.  ref_err is, as in the golden, the reference's own
+    distance from the 50-digit evaluation of the same formulas -- here the numpy restatement's, evaluated in
+    the test by the golden maker's mp_procrustes.  (With ref_err left at 0 the J = 65 case measured Z 5.7e-12
+    mm against a gate of 3.6e-12 on an MI355X: 6 ulp of coordinates that passed 4096 mm where the gate
+    counted ulps of an A below it; every other figure was inside.)
+    At J = 3 M has rank 2 exactly, the 50-digit SVD has no third singular value to order by, and ref_err
+    stays 0: every gate is the plain 8 ulp.  What ref_err absorbs at J = 65, the conditioning of the pose,
+    is therefore bounded on the inputs instead: R is the orthogonal polar factor of M and moves by about
+    eps / (s1 - |s2|) per unit rounding (s2 = 0 here), and t = a_bar - scale * b_bar R multiplies that by a
+    centroid as large as the coordinates, so 8 ulp for t needs s1 of a few tenths.  Pairs are drawn from the
+    seeded stream until five have s1 >= 0.25; three joints nearer a line approach the rank-1 case that has no
+    defined result (csrc/pose3d.hip).  The first pair dropped has s1 = 0.0026; there numpy itself is 114 ulp
+    from the 50-digit t.  With reflection 'best' the kernel's R and t must match one of numpy's two
+    completions of U; both poses lie in planes, so Z, d and the scale do not see the sign."""
+    from posu import ops
+    rng = np.random.RandomState(17)
+    pairs = []
+    while len(pairs) < 5:
+        pa, pb = rs.make_pair(rng, J, mirrored=bool(len(pairs) & 1))
+        s1 = np.linalg.svd(rs._normalise(pa, pb)[0], compute_uv=False)[1]
+        if J > 3 or s1 >= 0.25:
+            pairs.append((pa, pb))
+    A, B = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
+    a, b = _dev(A, cuda), _dev(B, cuda)
+    for scaling, reflection in rs.SETTINGS:
+        d, Z, R, scale, t = _host(ops.procrustes(a, b, scaling, reflection))
+        assert Z.shape == (5, J, 3) and R.shape == (5, 3, 3) and t.shape == (5, 3) and d.shape == scale.shape == (5,)
+        for n in range(5):
+            refs = _numpy_references(A[n], B[n], scaling, reflection, J == 3)
+            rd, rZ, _, rscale, _ = refs[0]
+            ref_z, ref_d, ref_t = _restatement_err(A[n], B[n], scaling, reflection, refs[0]) if J > 3 else (0.0, 0.0, 0.0)
+            gz, gd, gt = z_gate(ref_z, A[n]), d_gate(ref_d), z_gate(ref_t, A[n])
+            ez, ed = float(np.abs(Z[n] - rZ).max()), float(abs(d[n] - rd))
+            # R and t against the completion they are nearer to (one reference unless rank 2 and 'best')
+            er, et = min((float(np.abs(R[n] - r[2]).max()), float(np.abs(t[n] - r[4]).max())) for r in refs)
+            orth = float(np.abs(R[n].T.dot(R[n]) - np.eye(3)).max())
+            ld = np.longdouble
+            form = float(np.abs(ld(scale[n]) * B[n].astype(ld).dot(R[n].astype(ld)) + t[n].astype(ld)
+                                - Z[n].astype(ld)).max())
+            print('procrustes J=%d scaling=%s reflection=%s pose %d: Z %.2e scale*B*R+t %.2e (gate %.2e) t %.2e (gate '
+                  '%.2e) d %.2e (gate %.2e) R %.2e RtR-I %.2e' % (J, scaling, reflection, n, ez, form, gz, et, gt, ed, gd,
+                                                                  er, orth))
+            assert ez <= gz and ed <= gd and form <= gz and et <= gt
+            assert er <= 1e-13 and orth <= 1e-13
+            assert abs(scale[n] - rscale) <= 1e-14 * max(1.0, scale[n])
+            assert reflection == 'best' or (np.linalg.det(R[n]) < 0) == reflection
+            assert scaling or scale[n] == 1.0
+
+
 def test_pose_utils_procrustes_keeps_the_reference_interface(golden, cuda):
     from posu import ops
     from utils.pose_utils import PoseUtils

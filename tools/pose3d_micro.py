@@ -8,8 +8,16 @@ host, wall clock, once.
     python tools/pose3d_micro.py [--groups 2048] [--reps 25] [--out profiles/r10/pose3d_micro.txt]
 
 Prints one JSON line per kernel and writes the same lines to --out.
+
+    python tools/pose3d_micro.py --digest
+
+No timing: the three entry points on small seeded inputs that reach every branch (J = 3, 16 and 65, every
+reflection / scaling setting, a coplanar pose and one whose joints all coincide; limbs shared and per group,
+a NaN pose) and one sha1 per output tensor over its raw bytes, so NaN payloads count.  Two builds
+(tools/with_lib.py) compute the same bits when their listings are equal line for line.
 """
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -41,8 +49,49 @@ def event_ms(fn, warmup, reps):
     return statistics.median(out), min(out), max(out)
 
 
+def sha(t):
+    return hashlib.sha1(t.contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()[:12]
+
+
+def digest():
+    dev = torch.device('cuda', 0)
+
+    def line(tag, *outs):
+        torch.cuda.synchronize()
+        print('%-58s %s' % (tag, ' '.join(sha(o) for o in outs)), flush=True)
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    rng = np.random.RandomState(21)
+    for J in (3, 16, 65):
+        pairs = [rs.make_pair(rng, J, mirrored=bool(n & 1)) for n in range(7)]   # seven poses: two blocks
+        A, B = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
+        A[2], B[2] = A[2] * [1, 1, 0] + [0, 0, 700.0], B[2] * [1, 1, 0] + [0, 0, -300.0]   # coplanar: rank-2 M
+        B[4] = B[4, 0]                                                              # all joints equal: 0 / 0
+        for scaling, reflection in rs.SETTINGS:
+            line('procrustes J=%d scaling=%d reflection=%s' % (J, scaling, reflection),
+                 *ops.procrustes(up(A), up(B), scaling, reflection))
+    for J in (16, 65):
+        X, gt, R, T = rs.make_groups(rng, 3, 4, J)
+        gt[1, 2] = gt[1, 2, 0]
+        args = [up(a) for a in (X, gt, R, T)]
+        for yes in (False, True):
+            line('pose3d_errors J=%d procrustes=%d' % (J, yes), *ops.pose3d_errors(*args, procrustes=yes,
+                                                                                  return_aligned=True))
+    for per_group in (False, True):
+        poses, limb, _ = rs.make_limb_cases(300 + per_group, 70, per_group)
+        poses[5, 9] = np.nan
+        line('limb_break per_group=%d' % per_group,
+             *ops.limb_break(up(poses), up(rs.PARENT), up(limb), 0.4, return_worst=True))
+    chain = np.arange(-1, 64, dtype=np.int32)                                        # 65 joints: the stride wraps
+    poses = rng.randn(5, 65, 3) * 300
+    line('limb_break J=65', *ops.limb_break(up(poses), up(chain), up(np.full(65, 420.0)), 0.4, return_worst=True))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--digest', action='store_true', help='no timing: one sha1 per output tensor at small shapes')
     ap.add_argument('--groups', type=int, default=2048)
     ap.add_argument('--views', type=int, default=4)
     ap.add_argument('--joints', type=int, default=16)
@@ -50,6 +99,8 @@ def main():
     ap.add_argument('--reps', type=int, default=25)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'r10', 'pose3d_micro.txt'))
     args = ap.parse_args()
+    if args.digest:
+        return digest()
     if args.reps < 20:
         ap.error('--reps must be at least 20')
     dev = torch.device('cuda', 0)

@@ -8,8 +8,15 @@ on the host.  H36M training-set size by default: 2215 groups x 4 views x 16 join
 
 Wall clock around whole calls (host work is part of both), after warm-up, median of the repeats; the two
 kernels alone are also event-timed on prepared device tensors.  Prints JSON lines and writes them to --out.
+
+    python tools/pseudo_label_micro.py --digest
+
+No timing: the fp64 geometry entry points (posu_triangulate_dlt, posu_ransac_inliers, posu_reproject,
+posu_pseudo_label_sweep, posu_pckh_counts) on small seeded inputs that reach every branch, one sha1 per output
+tensor.  Two builds (tools/with_lib.py) compute the same bits when their listings are equal line for line.
 """
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -99,13 +106,93 @@ def event_ms(fn, warmup, reps):
     return statistics.median(out), min(out), max(out)
 
 
+def sha(t):
+    return hashlib.sha1(t.contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()[:12]
+
+
+def digest():
+    import pseudo_label_restatement as rs
+    dev = torch.device('cuda', 0)
+
+    def line(tag, *outs):
+        torch.cuda.synchronize()
+        print('%-66s %s' % (tag, ' '.join(sha(o) for o in outs)), flush=True)
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    # triangulation: V = 2, 3, 4 take the register kernel, 5 and 16 the folded one.  Seven groups of 16 joints
+    # are two blocks.  View v of group g is camera v % 4 of rig g + v // 4; the pixels are the pinhole
+    # projections plus noise; the mask hides views at random and leaves joints 3 (one view) and 7 (none).
+    G, J = 7, 16
+    poses = syn.synthetic_poses3d(G)
+    X1 = np.concatenate([poses, np.ones((G, J, 1))], axis=2)
+    for distortion in (True, False):
+        M4, I4 = camera_tables(syn.group_cameras(G, distortion=distortion), 4, no_distortion=not distortion)
+        for V in (2, 3, 4, 5, 16):
+            pick = [[((g + v // 4) % G, v % 4) for v in range(V)] for g in range(G)]
+            M = np.stack([[M4[a, b] for a, b in row] for row in pick])
+            intr = np.stack([[I4[a, b] for a, b in row] for row in pick])
+            P = np.einsum('gvrc,gjc->gvjr', M, X1)
+            r = np.random.default_rng(100 + V)
+            xy = P[..., :2] / P[..., 2:] + r.normal(0, 1.5, size=(G, V, J, 2))
+            vis = (r.uniform(size=(G, V, J)) < 0.7).astype(np.uint8)
+            vis[:, 1:, 3] = 0
+            vis[:, 0, 3] = 1
+            vis[:, :, 7] = 0
+            Md, Id, visd = up(M), up(intr), up(vis)
+            for dt in (torch.float32, torch.float64):
+                xyd = up(xy).to(dt)
+                tag = 'triangulate_dlt V=%d %s %s' % (V, str(dt).split('.')[1], 'distorted' if distortion else 'pinhole')
+                line(tag, ops.triangulate_dlt(Md, Id, xyd, None, undistort=distortion),
+                     ops.triangulate_dlt(Md, Id, xyd, visd, undistort=distortion))
+            if V == 4:
+                xv = up(np.ascontiguousarray(xy.transpose(1, 0, 2, 3)))
+                line('triangulate_dlt V=4 float64 view-major', ops.triangulate_dlt(Md, Id, xv, visd, distortion, True))
+
+    # the per-threshold entry points and the sweep at the GPU tests' cases (tests/pseudo_label_restatement.py)
+    cases = [(name, rs.make_inputs(rs.SEEDS[name], rs.CASES[name][0], rs.CASES[name][1]), 4, rs.CASES[name][1],
+              rs.CASES[name][2]) for name in rs.CASES]
+    cases.append(('v3', rs.make_v3_inputs(), 3, True, [0.6]))
+    for name, inp, V, distortion, thresholds in cases:
+        M, intr = (up(a) for a in camera_tables(inp['cams'], V, no_distortion=not distortion))
+        loc = up(inp['locations'])
+        g = len(inp['cams']) // V
+        xy = loc[:, :, :2].double().reshape(g, V, -1, 2).contiguous()
+        conf = loc[:, :, 2].reshape(g, V, -1).contiguous()
+        hide = conf > 0.6                                  # a mask that hides views
+        for inliers in rs.INLIERS:
+            line('%s ransac_inliers INLIERS=%d' % (name, inliers),
+                 ops.ransac_inliers(M, intr, xy, None, rs.REPROJ_THRE, inliers, undistort=distortion),
+                 ops.ransac_inliers(M, intr, xy, hide, rs.REPROJ_THRE, inliers, undistort=distortion))
+        line('%s reproject' % name, *(ops.reproject(M, intr, xy, None, undistort=distortion) +
+                                      ops.reproject(M, intr, xy, hide, undistort=distortion)))
+        for use_ransac in (True, False):
+            for inliers in rs.INLIERS:
+                masks, proj = ops.pseudo_label_sweep(M, intr, xy, conf, thresholds, rs.REPROJ_THRE, inliers, use_ransac,
+                                                     undistort=distortion)
+                line('%s pseudo_label_sweep ransac=%d INLIERS=%d' % (name, use_ransac, inliers), masks, proj)
+                if inliers != rs.GOLDEN_INLIERS or not use_ransac:
+                    continue
+                t, n, nj = len(thresholds), g * V, xy.shape[2]
+                gt, head = up(inp['gt2d']), up(inp['headsizes'])
+                sel = [s for i in range(t) for s in (-1, -1, i)]
+                line('%s pckh_counts' % name,
+                     ops.pckh_counts(xy.reshape(n, nj, 2), masks.reshape(t * 3, n, nj), gt, head, V, 0.5,
+                                     pred_sets=proj.reshape(t, n, nj, 2), set_pred=sel),
+                     ops.pckh_counts(None, masks.reshape(t * 3, n, nj), None, None, V))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--digest', action='store_true', help='no timing: one sha1 per output tensor at small shapes')
     ap.add_argument('--groups', type=int, default=2215)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'r11', 'pseudo_label_micro.txt'))
     args = ap.parse_args()
+    if args.digest:
+        return digest()
     if args.reps < 20:
         ap.error('--reps must be at least 20')
     dev = torch.device('cuda', 0)
