@@ -328,6 +328,24 @@ int posu_bottleneck_s2_tail_next_fwd(int dtype, const void* t1, const void* x, i
                                      const float* shift, int Cout, void* y, const float* s1n, const float* b1n,
                                      void* t1n, void* stream);
 
+/* The two tails above with the block's own conv1 folded in (additive, ABI 16): each tile computes
+ *   t1 = relu(conv1_1x1(x) * s1 + b1)
+ * on its 9 x 33 window from x (zeros outside the image: conv2's padding) instead of reading it, so
+ * the block is ONE launch and t1 never exists in memory.  Arguments as above without t1, plus
+ * s1 / b1: conv1's folded BN [128] f32 (16-B aligned).  wstream:
+ * packing.pack_s2_tail_stream(conv2 pack, dual pack[, next conv1 pack], w1=conv1 pack [128][256]):
+ * conv1's 8 k-steps in front, [4][92][2][64][8] (chained: [4][108]...).  y (and t1n) are
+ * bit-identical to posu_conv2d_fwd(conv1) followed by posu_bottleneck_s2_tail[_next]_fwd. */
+int posu_bottleneck_s2_front_tail_fwd(int dtype, const void* x, int N, int H, int W, int C, int P, const float* s1,
+                                      const float* b1, const void* wstream, long long wstream_bytes,
+                                      const float* s2, const float* b2, const float* shift, int Cout, void* y,
+                                      void* stream);
+int posu_bottleneck_s2_front_tail_next_fwd(int dtype, const void* x, int N, int H, int W, int C, int P,
+                                           const float* s1, const float* b1, const void* wstream,
+                                           long long wstream_bytes, const float* s2, const float* b2,
+                                           const float* shift, int Cout, void* y, const float* s1n,
+                                           const float* b1n, void* t1n, void* stream);
+
 /* The same fused block for the first Bottleneck of layer1 (lib/models/pose_resnet.py:61-99
  * with the downsample branch, pose_resnet.py:136-141): conv3/bn3 and the 1x1 downsample/bn
  * share one accumulator (as in posu_conv1x1_dual_fwd),

@@ -26,6 +26,9 @@ struct TailGeom {
   void* t1n;
   long long wseg;  // the weight stream's 64-B segments (warm-up, gemm_common.h)
   int warm;        // warm-up workgroups (0: none)
+  // FRONT (the strided tail): this block's own conv1 + BN1 + ReLU computed from x (t1 = nullptr)
+  const float* s1;
+  const float* b1;
 };
 
 // ---- the weight stream of one wave: fragment j (n-tile j of the wave's 32 output channels) of k-step
@@ -240,13 +243,15 @@ __device__ __forceinline__ void kblock(f32x4 (&acc)[MT][2], WS& ws, int p0, cons
 // `act_bytes` the largest activation, `need` the bytes of the stream the variant reads.
 inline int tail_operands(TailGeom& g, const std::string& what, const void* t1, const void* x, int N, int H,
                          const void* wstream, long long wstream_bytes, const float* s2, const float* b2,
-                         const float* s3, const float* b3, void* y, const float* s1n, const float* b1n, void* t1n) {
-  POSU_REQUIRE(t1 && x && wstream && s2 && b2 && b3 && y, what + ": null pointer");
+                         const float* s3, const float* b3, void* y, const float* s1n, const float* b1n, void* t1n,
+                         bool front = false, const float* s1 = nullptr, const float* b1 = nullptr) {
+  // front: conv1 runs inside the tail -- its BN in place of its output t1
+  POSU_REQUIRE((front ? s1 && b1 : t1 != nullptr) && x && wstream && s2 && b2 && b3 && y, what + ": null pointer");
   POSU_REQUIRE(x != y && t1 != y, what + ": the output must not alias an input");
   POSU_REQUIRE(!t1n || (s1n && b1n && t1n != y && t1n != x && t1n != t1),
                what + ": the next conv1 needs its BN and an output that aliases no other operand");
   g = TailGeom{t1, x, y, static_cast<const uint4*>(wstream), s2, b2, s3, b3, N, H, s1n, b1n, t1n, wstream_bytes / 64,
-               warm_wgs(wstream_bytes)};
+               warm_wgs(wstream_bytes), s1, b1};
   return POSU_OK;
 }
 
@@ -260,7 +265,8 @@ inline int tail_sizes(const TailGeom& g, const std::string& what, int hmult, lon
   for (const void* p : {g.t1, g.x, static_cast<const void*>(g.y), static_cast<const void*>(g.wst),
                         static_cast<const void*>(g.s3), static_cast<const void*>(g.b3),
                         static_cast<const void*>(g.t1n), static_cast<const void*>(g.s1n),
-                        static_cast<const void*>(g.b1n)})
+                        static_cast<const void*>(g.b1n), static_cast<const void*>(g.s1),
+                        static_cast<const void*>(g.b1)})
     POSU_REQUIRE((reinterpret_cast<size_t>(p) & 15) == 0, what + ": pointers must be 16-byte aligned");
   return POSU_OK;
 }

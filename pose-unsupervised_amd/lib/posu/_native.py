@@ -53,6 +53,9 @@ _SIGNATURES = {
                                              _p, _p],
     'posu_bottleneck_s2_tail_fwd': [_i, _p, _p, _i, _i, _i, _i, _i, _p, _ll, _p, _p, _p, _i, _p, _p],
     'posu_bottleneck_s2_tail_next_fwd': [_i, _p, _p, _i, _i, _i, _i, _i, _p, _ll, _p, _p, _p, _i, _p, _p, _p, _p, _p],
+    'posu_bottleneck_s2_front_tail_fwd': [_i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _ll, _p, _p, _p, _i, _p, _p],
+    'posu_bottleneck_s2_front_tail_next_fwd': [_i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _ll, _p, _p, _p, _i, _p, _p, _p,
+                                               _p, _p],
     'posu_bottleneck_down_fwd': [_i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     'posu_conv2d_fwd': [_i, _p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _i, _i, _p],
     'posu_deconv4x4s2_fwd': [_i, _p, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _i, _p],

@@ -36,7 +36,7 @@ def mfma_fragments(wpk):
     return wpk.reshape(co // 16, 16, k // 32, 4, 8).permute(0, 2, 3, 1, 4).reshape(co // 16, k // 32, 64, 8)
 
 
-def pack_s2_tail_stream(w2pk, wdual, w1n=None):
+def pack_s2_tail_stream(w2pk, wdual, w1n=None, w1=None):
     """The per-wave weight streams of posu_bottleneck_s2_tail_fwd (csrc/tail_s2.hip) from the conv2
     [128][1152] (posu_conv2d_fwd) and dual [512][384] (pack_dual_1x1_weight) packs:
     [4 channel groups][84 k-steps][2 n-tiles][64 lanes][8].  Group cq, k-step p < 36: conv2 n-tile
@@ -45,10 +45,21 @@ def pack_s2_tail_stream(w2pk, wdual, w1n=None):
 
     w1n (the next identity block's conv1 pack [128][512], posu_bottleneck_s2_tail_next_fwd): after
     dual chunk nc's 12 k-steps come the next conv1's 4 k-steps over that chunk's 128 y channels --
-    [4][100][2][64][8], p = 36 + 16 nc + 12 + c: conv1n n-tile 2 cq + j, k-step 4 nc + c."""
+    [4][100][2][64][8], p = 36 + 16 nc + 12 + c: conv1n n-tile 2 cq + j, k-step 4 nc + c.
+
+    w1 (this block's own conv1 pack [128][256], posu_bottleneck_s2_front_tail[_next]_fwd): its 8 k-steps
+    in front of conv2's -- [4][92 or 108][2][64][8], p < 8: conv1 n-tile 2 cq + j, k-step p; every later
+    k-step 8 further."""
     if tuple(w2pk.shape) != (128, 1152) or tuple(wdual.shape) != (512, 384):
         raise ValueError('pack_s2_tail_stream: conv2 pack [128][1152] and dual pack [512][384] expected, got %s / %s'
                          % (tuple(w2pk.shape), tuple(wdual.shape)))
+    if w1 is not None:
+        if tuple(w1.shape) != (128, 256):
+            raise ValueError('pack_s2_tail_stream: the block\'s conv1 pack must be [128][256], got %s' % (tuple(w1.shape),))
+        if w1.dtype != w2pk.dtype:
+            raise ValueError('pack_s2_tail_stream: the conv1 pack is %s, the conv2 pack %s' % (w1.dtype, w2pk.dtype))
+        ff = mfma_fragments(w1).reshape(4, 2, 8, 64, 8).permute(0, 2, 1, 3, 4)   # [cq][8][j][64][8]
+        return torch.cat([ff, pack_s2_tail_stream(w2pk, wdual, w1n)], dim=1).contiguous()
     f2 = mfma_fragments(w2pk)                                     # [8][36][64][8]
     s2 = f2.reshape(4, 2, 36, 64, 8).permute(0, 2, 1, 3, 4)       # [cq][36][j][64][8]
     fd = mfma_fragments(wdual)                                    # [32][12][64][8]

@@ -270,6 +270,17 @@ CHAINED_TAILS = True
 # layer2's strided tail chained with block 1's conv1 (posu_bottleneck_s2_tail_next_fwd, round 4;
 # under CHAINED_TAILS too)
 S2_CHAIN = True
+# layer2's first Bottleneck as ONE launch: its conv1 folded into the strided tail, which computes
+# relu(bn1(conv1(x))) on each tile's window instead of reading t1 (posu_bottleneck_s2_front_tail[_next]_fwd,
+# bit-identical).  True: always; False: where the autotuner measured it faster (S2_FRONT_TUNE), else the
+# conv1 launch, then the tail reading its output.  Off by default like every untuned choice: a plan that
+# was never tuned launches what it always launched (tests/test_plan_trace.py pins that sequence)
+S2_FRONT = False
+# the autotuner times both forms of that block on its real operands and keeps the faster in the tile table
+# (key ('s2_front', dtype, x shape, chained) -> 1 / 0, persisted with the tiles by bench.py --tune-file);
+# False: never the one-launch form unless S2_FRONT forces it (bench.py --plan-flag S2_FRONT_TUNE=0 is the
+# A/B handle; the headline measured 2.255 vs 2.308 ms with the one-launch form, profiles/r10)
+S2_FRONT_TUNE = True
 # the identity Bottlenecks at 384x384 (R152, BASELINE configs[4]) as conv1 + the streamed tail
 # (round 5): layer3 at W = 24 (not chained), layer2 at W = 48 (chained).  Chaining layer3's W = 24 tails
 # like the 256x256 ones (2-row tiles, three m-tiles per wave, round 6) measured even with each conv1 a
@@ -357,7 +368,9 @@ class _Block:
 
         'fused' / 'fused_down'   posu_bottleneck_fwd / posu_bottleneck_down_fwd
         'down_tail'              conv1, posu_bottleneck_down_tail_stream_fwd (chained: with s1n / b1n)
-        's2_tail'                conv1, posu_bottleneck_s2_tail_fwd (chained: .._s2_tail_next_fwd)
+        's2_tail'                conv1, posu_bottleneck_s2_tail_fwd (chained: .._s2_tail_next_fwd); S2_FRONT, or
+                                 tuned so (S2_FRONT_TUNE): posu_bottleneck_s2_front_tail_fwd (.._next_fwd)
+                                 alone, conv1 inside it
         'tail'                   conv1 (unless handed in), posu_bottleneck_tail_stream_fwd (chained 'next':
                                  .._stream_next_fwd, 'layer': .._stream_chain_fwd)
         'dual'                   conv1 (unless handed in), conv2, the conv3 | downsample dual GEMM
@@ -373,8 +386,9 @@ class _Block:
         self.code = code
         self.kind = None     # 'l1' / 'l2' / 'l3': the identity block of that layer the streamed tail is built for
         # the fused kernels' packs by variant: 'fused' (conv1, conv3 with permuted K), 'fused_down' ([w3*s3 |
-        # wd*sd], permuted conv3 K), 'tail' / 'down_tail' / 's2_tail' (the per-wave weight streams) and
-        # '.._next' / 'tail_layer' (the streams with the chained conv1 appended)
+        # wd*sd], permuted conv3 K), 'tail' / 'down_tail' / 's2_tail' (the per-wave weight streams),
+        # '.._next' / 'tail_layer' (the streams with the chained conv1 appended) and 's2_front' / 's2_front_next'
+        # (the strided tail's streams with the block's own conv1 in front, S2_FRONT)
         self.packs = {}
         self.chain = None    # the next block's conv1 (_Conv) where this block's tail can chain it
         self.xchain = None   # the next layer's first conv1 (_Conv), chained by this layer's last tail
@@ -394,6 +408,7 @@ class _Block:
                                torch.ones(self.dual.cout, device=self.dual.shift.device))
             if self._built_for('s2_tail'):
                 self.packs['s2_tail'] = pack_s2_tail_stream(c2.w, self.dual.w)
+                self.packs['s2_front'] = pack_s2_tail_stream(c2.w, self.dual.w, w1=self.convs[0].w)
             return
         for nm in names:
             self.convs.append(_Conv(getattr(blk, nm), getattr(blk, 'bn' + nm[-1]), True, code, bk))
@@ -439,6 +454,7 @@ class _Block:
         elif 's2_tail' in self.packs and nxt.kind == 'l2':
             self.chain = nxt.convs[0]
             self.packs['s2_tail_next'] = pack_s2_tail_stream(c2.w, self.dual.w, self.chain.w)
+            self.packs['s2_front_next'] = pack_s2_tail_stream(c2.w, self.dual.w, self.chain.w, w1=self.convs[0].w)
 
     def link_layer(self, first):
         """Chain this last identity block's tail with the next layer's first block's conv1 (1x1 / stride 1,
@@ -529,13 +545,8 @@ class _Block:
                 c1(x, code), x, self.packs['down_tail_next' if chained else 'down_tail'], c2.scale, c2.shift,
                 self.dscale, self.dual.shift, code, s1n=s1n, b1n=b1n, out=out)
         if variant == 's2_tail':
-            c1, c2 = cs
-            if chained:
-                n1 = self.chain
-                return ops.bottleneck_s2_tail_next_nhwc(c1(x, code), x, self.packs['s2_tail_next'], c2.scale, c2.shift,
-                                                        self.dual.shift, n1.scale, n1.shift, code, out=out)
-            return ops.bottleneck_s2_tail_nhwc(c1(x, code), x, self.packs['s2_tail'], c2.scale, c2.shift,
-                                               self.dual.shift, code, out=out), None
+            front = S2_FRONT or (S2_FRONT_TUNE and self._front_tuned(x, code, chained, out))
+            return self._s2_tail(x, code, chained, out, front)
         if variant == 'dual':
             return self.dual(cs[1](cs[0](x, code) if t1 is None else t1, code), x, code, out=out), None
         res = self.down(x, code) if self.down is not None else x
@@ -543,6 +554,51 @@ class _Block:
         for c in cs[:-1]:
             y = c(y, code)
         return cs[-1](y, code, residual=res, out=out), None
+
+    def _s2_tail(self, x, code, chained, out, front):
+        """The 's2_tail' variant's launches: front -- the block's conv1 inside the strided tail, one launch --
+        or the conv1 launch and the tail reading its output.  Bit-identical (the same K order per accumulator)
+        unless conv1's tuned tile is the two-K-group one."""
+        c1, c2 = self.convs
+        n1 = self.chain
+        if front:
+            if chained:
+                return ops.bottleneck_s2_front_tail_next_nhwc(
+                    x, c1.scale, c1.shift, self.packs['s2_front_next'], c2.scale, c2.shift, self.dual.shift,
+                    n1.scale, n1.shift, code, out=out)
+            return ops.bottleneck_s2_front_tail_nhwc(x, c1.scale, c1.shift, self.packs['s2_front'], c2.scale,
+                                                     c2.shift, self.dual.shift, code, out=out), None
+        if chained:
+            return ops.bottleneck_s2_tail_next_nhwc(c1(x, code), x, self.packs['s2_tail_next'], c2.scale, c2.shift,
+                                                    self.dual.shift, n1.scale, n1.shift, code, out=out)
+        return ops.bottleneck_s2_tail_nhwc(c1(x, code), x, self.packs['s2_tail'], c2.scale, c2.shift,
+                                           self.dual.shift, code, out=out), None
+
+    def _front_tuned(self, x, code, chained, out):
+        """The tuned choice between the two forms of _s2_tail for this input (S2_FRONT_TUNE): while the
+        autotuner runs, both are timed on the real operands like the tiles of _tuned (two passes, the second
+        in reverse order, each form's best) and the faster is kept in the tile table; otherwise the stored
+        choice, or -- a plan that was never tuned -- the two launches."""
+        key = ('s2_front', code, tuple(x.shape), bool(chained))
+        if _Tuner.active and key not in _TUNE_CACHE:
+            seen = list(_Tuner.seen)
+            times = {}
+            for order in ((0, 1), (1, 0)):
+                for f in order:
+                    self._s2_tail(x, code, chained, out, bool(f))   # (the first call tunes conv1's tile)
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    for _ in range(_Tuner.reps):
+                        self._s2_tail(x, code, chained, out, bool(f))
+                    b.record()
+                    b.synchronize()
+                    ms = a.elapsed_time(b)
+                    times[f] = min(ms, times.get(f, ms))
+            _TUNE_CACHE[key] = int(times[1] < times[0])
+            _TUNE_TIMES[key] = times
+            if _TUNE_CACHE[key]:
+                _Tuner.seen[:] = seen   # conv1 is no launch of this forward: nothing for the in-context stage
+        return bool(_TUNE_CACHE.get(key, 0))
 
     def __call__(self, x, code, out=None):
         """The block alone, unchained: y."""

@@ -6,7 +6,8 @@ Per launch: the bytes a kernel must move at least -- every input activation it n
 once.  The launch list is the default plan's (plan.py: fused stem over all views, fused layer1
 blocks, layer2 conv1 + the strided tail chained with block 1's conv1, chained streamed tails, conv
 launches for layer3 block 0 and layer4, deconv1, deconv2, deconv3 with the fused head writing f32
-heatmaps only): 30 launches.  Comparing it with the PMC traffic of the same launches
+heatmaps only): 30 launches; s2_front=True: the plan.S2_FRONT / tuned form, layer2 block 0 as one launch, 29).
+Comparing it with the PMC traffic of the same launches
 (FETCH_SIZE x 2 + WRITE_SIZE, tools/pmc_traffic.py) gives each kernel's over-fetch.
 """
 
@@ -14,7 +15,7 @@ heatmaps only): 30 launches.  Comparing it with the PMC traffic of the same laun
 _R50 = ((3, 64, 64, 256, 64), (4, 128, 256, 512, 64), (6, 256, 512, 1024, 32), (3, 512, 1024, 2048, 16))
 
 
-def r50_256_launches(n=128, es=2, joints=17):
+def r50_256_launches(n=128, es=2, joints=17, s2_front=False):
     """[(name, read_bytes, write_bytes)] for one forward of n frames (es: activation bytes)."""
     out = []
     act = lambda hw, c: n * hw * hw * c * es  # noqa: E731
@@ -28,11 +29,17 @@ def r50_256_launches(n=128, es=2, joints=17):
         out.append(('layer1.%d bottleneck64' % b, act(64, 256) + wb(64, 256) + wb(64, 576) + wb(256, 64),
                     act(64, 256)))
     # layer2: conv1 at 64x64, the strided tail (chained), chained tails, the last tail
-    out.append(('layer2.0 conv1', act(64, 256) + wb(128, 256), act(64, 128)))
-    # the strided tail chained with block 1's conv1 (S2_CHAIN): y and block 1's t1 written
-    out.append(('layer2.0 strided tail + layer2.1 conv1',
-                act(64, 128) + act(32, 256) + wb(128, 1152) + wb(512, 384) + wb(128, 512),
-                act(32, 512) + act(32, 128)))
+    if s2_front:
+        # the whole block in one launch (S2_FRONT): x read once, t1 never in memory
+        out.append(('layer2.0 conv1 + strided tail + layer2.1 conv1',
+                    act(64, 256) + wb(128, 256) + wb(128, 1152) + wb(512, 384) + wb(128, 512),
+                    act(32, 512) + act(32, 128)))
+    else:
+        out.append(('layer2.0 conv1', act(64, 256) + wb(128, 256), act(64, 128)))
+        # the strided tail chained with block 1's conv1 (S2_CHAIN): y and block 1's t1 written
+        out.append(('layer2.0 strided tail + layer2.1 conv1',
+                    act(64, 128) + act(32, 256) + wb(128, 1152) + wb(512, 384) + wb(128, 512),
+                    act(32, 512) + act(32, 128)))
     for b in (1, 2):
         out.append(('layer2.%d chained tail' % b, act(32, 128) + act(32, 512) + wb(128, 1152) + wb(512, 128) +
                     wb(128, 512), act(32, 512) + act(32, 128)))

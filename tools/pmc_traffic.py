@@ -80,8 +80,10 @@ def main():
     from posu import roofline
     split = any('f16s_t' in x[1] for x in f)   # the fp16x3 plan: its own launch list (no algorithmic table)
     line['plan'] = 'fp16x3' if split else 'default (bf16 / fp16)'
-    if not split and len(f) == len(roofline.r50_256_launches()):
-        alg = roofline.r50_256_launches()
+    # the default plan's list, with layer2 block 0 as one launch (plan.S2_FRONT, or tuned so) or as conv1 + the tail
+    algs = [roofline.r50_256_launches(s2_front=sf) for sf in (True, False)]
+    if not split and len(f) in [len(x) for x in algs]:
+        alg = next(x for x in algs if len(x) == len(f))
         line['algorithmic_bytes'] = sum(r + wr for _, r, wr in alg)
         line['traffic_over_algorithmic'] = round(line['traffic_bytes'] / line['algorithmic_bytes'], 4)
     print(json.dumps(line))

@@ -1,6 +1,8 @@
 """Micro-benchmark of layer2's first Bottleneck tail at the bench shape (128 frames, bf16):
 conv2 (3x3 / stride 2) + the conv3 | downsample dual GEMM as two launches (the plan's autotuned
-tiles are not used: heuristic tiles) vs posu_bottleneck_s2_tail_fwd; HIP events, min over rounds,
+tiles are not used: heuristic tiles) vs posu_bottleneck_s2_tail_fwd; the chained tail vs the tail +
+the next conv1 launch; and the block's conv1 launch + the chained tail vs the one-launch block
+(posu_bottleneck_s2_front_tail_next_fwd, conv1 inside the tail).  HIP events, min over rounds,
 outputs checked bit for bit.
 
     python tools/s2tail_micro.py [--n 128] [--reps 20] [--rounds 3] [--lib PATH]
@@ -84,17 +86,35 @@ def main():
     def chained():
         ops.bottleneck_s2_tail_next_nhwc(t1, x, wsn, s2, b2, shift, s1n, b1n, BF16, out=y3, t1n=t1n)
 
+    # the whole block: conv1 (a launch of its own, heuristic tile) + the chained tail reading its output
+    # vs the front-fused chained tail, which computes conv1 on each tile's window
+    p1 = packing.pack_conv_weight((torch.randn(128, 256, 1, 1, generator=g) * 0.09).to(dev), 256, bk, dt)
+    s1, b1 = (torch.rand(128, generator=g) + 0.5).to(dev), (torch.randn(128, generator=g) * 0.1).to(dev)
+    wsf = packing.pack_s2_tail_stream(p2, pd, p1n, w1=p1)
+    t1c = torch.empty_like(t1)
+    y4, y5 = torch.empty_like(y2), torch.empty_like(y2)
+    t1n4, t1n5 = torch.empty_like(t1n), torch.empty_like(t1n)
+
+    def conv1_chained():
+        ops.conv2d_nhwc(x, p1, 128, 1, 1, 1, 0, s1, b1, None, True, BF16, out=t1c)
+        ops.bottleneck_s2_tail_next_nhwc(t1c, x, wsn, s2, b2, shift, s1n, b1n, BF16, out=y4, t1n=t1n4)
+
+    def front_chained():
+        ops.bottleneck_s2_front_tail_next_nhwc(x, s1, b1, wsf, s2, b2, shift, s1n, b1n, BF16, out=y5, t1n=t1n5)
+
     flop = 2.0 * a.n * 1024 * (1152 * 128 + 384 * 512)
     flop_c = flop + 2.0 * a.n * 1024 * 512 * 128
     nbytes = (t1.numel() + x.numel() // 4 + y1.numel()) * 2
     for name, fn, fl in (('two launches', two, flop), ('strided tail', fused, flop),
-                         ('tail + conv1', tail_conv1, flop_c), ('chained tail', chained, flop_c)):
+                         ('tail + conv1', tail_conv1, flop_c), ('chained tail', chained, flop_c),
+                         ('conv1 + chained', conv1_chained, flop_c + 2.0 * a.n * 4096 * 256 * 128),
+                         ('front chained', front_chained, flop_c + 2.0 * a.n * 4096 * 256 * 128)):
         us = timeit(fn, a.reps, a.rounds)
         print('%-14s %8.1f us  %6.1f TFLOP/s  %5.2f TB/s (algorithmic t1 + x/4 + y)'
               % (name, us, fl / us / 1e6, nbytes / us / 1e6))
     torch.cuda.synchronize()
     print('bit-identical:', bool(torch.equal(y1, y2)), 'chained:', bool(torch.equal(y3, y1)),
-          bool(torch.equal(t1n, t1r)))
+          bool(torch.equal(t1n, t1r)), 'front:', bool(torch.equal(y5, y4)), bool(torch.equal(t1n5, t1n4)))
 
 
 if __name__ == '__main__':
