@@ -80,7 +80,8 @@ const char* posu_last_error(void);
  * (posu_pck_accuracy, posu_grad_row_norms, posu_meters_update and their workspace queries) and the
  * 3-D evaluation protocol (posu_procrustes, posu_pose3d_errors, posu_limb_break) and the
  * pseudo-label round (posu_pseudo_label_workspace, posu_pseudo_label_sweep, posu_pckh_counts) and the
- * training sample (posu_sample_workspace, posu_sample_images, posu_sample_joints_targets).  The
+ * training sample (posu_sample_workspace, posu_sample_images, posu_sample_joints_targets) and the
+ * validation epoch (posu_decode_views_workspace, posu_decode_views, posu_detection_counts).  The
  * ctypes binding refuses a library of another revision. */
 int posu_abi_version(void);
 
@@ -1052,6 +1053,56 @@ int posu_pseudo_label_sweep(const double* M, const double* intr, const double* x
 int posu_pckh_counts(const double* pred, const double* pred_sets, const int* set_pred,
                      const unsigned char* vis, const double* gt, const double* head, int B, int N, int J,
                      int V, double threshold, int* counts, void* stream);
+
+/* ------------------------------------------------------- validation epoch */
+/* The batch body of validate (lib/core/function.py:529-690) after the forwards, for all V (1..8) views
+ * in one launch (csrc/validate.hip), additive to ABI 16.  One wave per map (v, n, j).  Stream-ordered,
+ * no allocation, no synchronisation, no atomics.
+ *   outputs:  HOST array of V device pointers to the plain outputs [N, J, H, W] f32 (any 4-byte
+ *             alignment; rows of whole float4s in 16-byte aligned maps are moved with 16-byte accesses);
+ *   flipped:  NULL, or a HOST array of V device pointers to the outputs of the mirrored input, raw
+ *             (function.py:570-576).  The merged map is the reference's flip_back_th
+ *             (lib/utils/transforms.py:33-47), SHIFT_HEATMAP (function.py:579-582) and average (:583)
+ *             in posu_flip_back's expression: m = 0.5f * (o + F), F = flipped[n][perm[j]][y][W - 1 - xs],
+ *             xs = shift ? max(x - 1, 0) : x.  Without flipped, m = o;
+ *   perm:     NULL (identity) or [J] int32 DEVICE: the joint each joint swaps with (an entry outside
+ *             [0, J) reads the joint itself);
+ *   targets:  NULL, or a HOST array of V device pointers to the target heatmaps: then accuracy
+ *             (lib/core/evaluate.py:42-73, called per view at function.py:618-624) of the merged maps in
+ *             posu_pck_accuracy's arithmetic and layout: acc [V, J + 1] f64, avg [V] f64, cnt [V] int32,
+ *             step [2] f64, with workspace >= posu_decode_views_workspace(V, N, J) bytes, 4-byte aligned
+ *             (-1: V outside 1..8, N < 0, J < 1, or 2^31 maps and more).  Without targets these five may
+ *             be NULL and are not written;
+ *   affine64: NULL or [V * N, 2, 3] f64, view-major: the inverse crop affines of get_final_preds
+ *             (lib/core/inference.py:50-75);
+ *   decode:   posu_argmax2d_fwd's: the first maximum of m, coordinates zeroed when it is <= 0, with
+ *             post_process the +-0.25 px shift toward the larger neighbour when 1 < ix < W - 1 and
+ *             1 < iy < H - 1 (neighbours recomputed from the inputs), the f64 affine, the f32 store;
+ *   preds_out:  [rows, J, 3] f32, (x, y, maxval);  merged_out: NULL or [rows, J, H, W] f32, receives m.
+ *             Both are addressed by row = row0 + n * V + v, the reference's preds[k::nviews] order
+ *             (function.py:632-644): the pointers are the bases of the epoch's buffers, and
+ *             0 <= row0, row0 + V * N <= rows is required.  Rows outside that range are not touched.
+ * N == 0 returns POSU_OK without a launch. */
+long long posu_decode_views_workspace(int V, int N, int J);
+int posu_decode_views(const float* const* outputs, const float* const* flipped, const int* perm, int shift,
+                      const float* const* targets, const double* affine64, int V, int N, int J, int H, int W,
+                      int post_process, double thr, float* merged_out, float* preds_out, long long row0,
+                      long long rows, double* acc, double* avg, int* cnt, double* step, void* workspace,
+                      long long workspace_bytes, void* stream);
+
+/* The counts behind the evaluations validate ends with (function.py:678), for T (1..8) thresholds at once.
+ *   pred: [N, J, pred_stride] f32, pred_stride 2 or 3: x and y are read and widened to f64;
+ *   gt:   [N, J, 2] f64;  head: [N] f64;  vis: NULL (every joint counts) or [N, J] uint8;
+ *   thresholds: HOST array of T doubles;
+ *   d = sqrt(dx * dx + dy * dy) in f64, each operation rounded on its own, and a row is detected when
+ *     form 0: d <= head * thr   (MultiViewH36MCompatible.evaluate, lib/dataset/multiview_h36m_compatible.py:205-208)
+ *     form 1: d / head <= thr   (MPIIDatasetCompatible.evaluate, lib/dataset/mpii_compatible.py:173-175);
+ *   counts: [T, 2, J] int32, zeroed here on the stream: [t][0][j] rows with joint j visible and detected
+ *           at thresholds[t], [t][1][j] rows with joint j visible.
+ * Integer atomics: the result does not depend on the order.  N == 0 zeroes counts and launches nothing. */
+int posu_detection_counts(const float* pred, int pred_stride, const double* gt, const double* head,
+                          const unsigned char* vis, const double* thresholds, int T, int form, int N, int J,
+                          int* counts, void* stream);
 
 #ifdef __cplusplus
 }

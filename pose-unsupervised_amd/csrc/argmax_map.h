@@ -1,9 +1,24 @@
 // The argmax of one heatmap by one wave64 (get_max_preds, lib/core/inference.py:19-47), shared by
-// posu_argmax2d_fwd (heatmap.hip) and posu_pck_accuracy (train_metrics.hip).
+// posu_argmax2d_fwd (heatmap.hip), posu_pck_accuracy (train_metrics.hip) and posu_decode_views
+// (validate.hip).
 #pragma once
 #include "posu_common.h"
 
 namespace posu {
+
+// The lanes' (best, bidx) pairs -> the wave's on every lane: the larger value, the smaller index on a
+// tie.  A lane that met no element holds (-inf, 0x7fffffff).
+__device__ __forceinline__ void wave_argmax_lanes(float& best, int& bidx) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bidx, o, 64);
+    if (ov > best || (ov == best && oi < bidx)) {
+      best = ov;
+      bidx = oi;
+    }
+  }
+}
 
 // best / bidx on every lane: the maximum of h[0 .. HW) and its first (smallest) index; bidx =
 // 0x7fffffff when no element compares greater than -inf (an all -inf / NaN map).
@@ -33,15 +48,7 @@ __device__ __forceinline__ void wave_argmax(const float* __restrict__ h, int HW,
   } else {
     for (int i = lane; i < HW; i += 64) take(h[i], i);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bidx, o, 64);
-    if (ov > best || (ov == best && oi < bidx)) {
-      best = ov;
-      bidx = oi;
-    }
-  }
+  wave_argmax_lanes(best, bidx);
 }
 
 // (x, y) = (idx % W, floor(idx / W)), zeroed when maxval <= 0 (inference.py:38-45)

@@ -27,6 +27,12 @@ loss, ``accuracy`` on host copies of every view's heatmaps, the gradient-norm wa
 selection of the H36M samples -- stays on the device here (posu_pck_accuracy, posu_grad_row_norms,
 posu_meters_update; the selection is decided on the host from ``meta``), so between two log lines
 the host only enqueues.
+
+``validate_device`` / ``validate_batch_device`` are the same loop for an epoch that stays on the device:
+one posu_decode_views launch per batch does the flip-test merge, the decode and the accuracy of all
+views and writes into preallocated epoch buffers in the reference's row order; loss and accuracy meters
+live in a device table; the host reads the device only to print and once at the end.  ``validate`` and
+``validate_batch`` are unchanged.
 """
 import logging
 import os
@@ -142,10 +148,11 @@ class _DeviceMeters:
     """The loop's AverageMeters as one [M, 3] f64 device table (val, sum, count), updated by one
     posu_meters_update launch per step and read only to print."""
 
-    def __init__(self, device):
+    def __init__(self, device, names=METERS):
         self.device = device
-        self.table = torch.zeros((len(METERS), 3), dtype=torch.float64, device=device)
-        self.vals = torch.zeros((len(METERS),), dtype=torch.float64, device=device)
+        self.names = tuple(names)
+        self.table = torch.zeros((len(self.names), 3), dtype=torch.float64, device=device)
+        self.vals = torch.zeros((len(self.names),), dtype=torch.float64, device=device)
         self._weights = {}
         self._slots = {}
 
@@ -154,7 +161,7 @@ class _DeviceMeters:
         and, at function.py:380, for the consistent meter as well; 1 for the others; the accuracy slot
         is filled per step with the device value cnt."""
         if nsamples not in self._weights:
-            w = [float(nsamples) if name in ('loss', 'mse', 'consistent') else 1.0 for name in METERS]
+            w = [float(nsamples) if name in ('loss', 'mse', 'consistent') else 1.0 for name in self.names]
             self._weights[nsamples] = torch.tensor(w, dtype=torch.float64).to(self.device)
         return self._weights[nsamples]
 
@@ -168,7 +175,7 @@ class _DeviceMeters:
         The f32 scalars (the losses) and the f64 ones (accuracy, gradient norms) each reach the value
         vector as one stack and one index_copy_; then one posu_meters_update launch."""
         groups = {torch.float32: ([], []), torch.float64: ([], []), 'host': ([], [])}
-        for slot, name in enumerate(METERS):
+        for slot, name in enumerate(self.names):
             v = values.get(name)
             if v is None:
                 continue
@@ -187,15 +194,15 @@ class _DeviceMeters:
             self.vals.index_copy_(0, self._slot_index(tuple(slots)), stacked)
         w = self.weights(nsamples)
         if acc_weight is not None:
-            acc = METERS.index('acc')
+            acc = self.names.index('acc')
             w[acc:acc + 1].copy_(acc_weight.reshape(1))
-        ops.meters_update(self.table, self.vals, w, [name in values for name in METERS])
+        ops.meters_update(self.table, self.vals, w, [name in values for name in self.names])
 
     def read(self):
         """One device-to-host copy -> {name: AverageMeter}."""
         host = self.table.cpu().numpy()
         out = {}
-        for name, (val, total, count) in zip(METERS, host):
+        for name, (val, total, count) in zip(self.names, host):
             m = AverageMeter()
             m.val, m.sum, m.count = float(val), float(total), float(count)
             m.avg = m.sum / m.count if m.count else 0
@@ -513,3 +520,138 @@ def validate(config, loader, dataset, model_dict, criterion_dict, output_dir, wr
         _, perf_indicator = dataset.evaluate(all_preds[:, u, :],
                                              output_dir if config.DEBUG.SAVE_ALL_PREDS else None)
     return perf_indicator
+
+
+# slots of validate_device()'s device meter table (losses / avg_acc of function.py:542-543)
+VALID_METERS = ('loss', 'acc')
+
+
+def validate_batch_device(config, model, input, target, weight, meta, flip_pairs, criterion_dict, preds_out,
+                          heatmaps_out, row0):
+    """``validate_batch`` for an epoch that stays on the device: the same model runs, ``fuse_routing`` and loss
+    terms in the same order with the same ops, then one ``ops.decode_views`` call in place of the per-view
+    flip-back, accuracy and ``get_final_preds`` calls.
+
+    input: V x [N, 3, H, W] cuda; target / weight: V x [N, J, h, w] / [N, J, 1] (host or cuda); meta: V dicts with
+    host 'center', 'scale' ([N, 2]) and, for the AGGRE terms, 'source'.  preds_out [R, J, 3] f32 cuda and
+    heatmaps_out ([R, J, h, w] f32 cuda, or None: the merged heatmaps are not stored) are the epoch's buffers;
+    rows row0 + n * V + v are written, so that ``preds_out[row0 + k:row0 + V * N:V]`` is view k
+    (``preds[k::nviews]``).  Returns a dict of device tensors only: loss (0-dim f32), acc and cnt (0-dim f64:
+    the means over the views, what ``validate_batch`` returns as floats), acc_table ([V, J + 1] f64), output
+    (the V routed outputs before the flip-test merge) and rows (V * N).  Nothing is read from the device: the
+    H36M rows of the consistent loss are chosen on the host from ``meta``."""
+    from utils.transforms import batch_inverse_affines
+    device = input[0].device
+    nviews = len(input)
+    fuse = bool(config.NETWORK.AGGRE) and bool(getattr(config.TEST, 'FUSE_OUTPUT', False))
+    criterion = criterion_dict['mse_weights']
+    with torch.no_grad():
+        raw, agg = _run_model(model, input, False)
+        output = fuse_routing(raw, agg, fuse, meta) if fuse else raw
+        flipped = perm = None
+        if config.TEST.FLIP_TEST:
+            raw_f, agg_f = _run_model(model, input, True)
+            flipped = fuse_routing(raw_f, agg_f, fuse, meta) if fuse else raw_f
+            perm = torch.tensor(flip_pair_order(output[0].shape[1], flip_pairs or []), dtype=torch.int32).to(device)
+        target = [t.to(device) for t in target]
+        weight = [w.to(device) for w in weight]
+        loss = 0
+        for t, w, r in zip(target, weight, raw):   # on the raw outputs (function.py:589-595)
+            loss = loss + criterion(r, t, w)
+        if config.NETWORK.AGGRE:                   # function.py:597-609
+            if getattr(config.LOSS, 'USE_CONSISTENT_LOSS', False):
+                rows = [_h36m_rows(m) for m in meta]
+                if len(rows[0]) != 0:
+                    # select_out_h36m's rows through an index made on the host: a boolean mask is a nonzero
+                    # and a synchronisation
+                    index = [torch.tensor(r, dtype=torch.long).to(device) for r in rows]
+                    rh = torch.cat([r.index_select(0, k) for r, k in zip(raw, index)], dim=0)
+                    ah = torch.cat([a.index_select(0, k) for a, k in zip(agg, index)], dim=0)
+                    assert rh.shape[0] == ah.shape[0]
+                    loss = loss + ops.joints_mse(rh.contiguous(), ah.contiguous(), None) / rh.shape[1]
+            if getattr(config.DATASET, 'PSEUDO_LABEL_PATH', ''):
+                for t, w, o in zip(target, weight, output):
+                    loss = loss + criterion(o, t, w) * config.LOSS.MSE_LOSS_WEIGHT
+        h, w_ = output[0].shape[2], output[0].shape[3]
+        trans = np.concatenate([batch_inverse_affines(np.asarray(m['center']), np.asarray(m['scale']), [w_, h])
+                                for m in meta], axis=0)       # [V * N, 2, 3] f64, view-major: one upload
+        T = torch.from_numpy(np.ascontiguousarray(trans, dtype=np.float64)).to(device)
+        _, _, acc, _, _, step = ops.decode_views(
+            output, flipped=flipped, perm=perm, shift=bool(config.TEST.SHIFT_HEATMAP), targets=target, affine64=T,
+            post_process=bool(config.TEST.POST_PROCESS), preds_out=preds_out, merged_out=heatmaps_out, row0=row0)
+    return {'loss': loss, 'acc': step[0], 'cnt': step[1], 'acc_table': acc, 'output': output,
+            'rows': nviews * input[0].shape[0]}
+
+
+class ValidationResult:
+    """What ``validate_device`` leaves: perf_indicator and name_values (``dataset.evaluate``'s; 1000 and None on
+    the other ranks), locations ([nsamples, J, 3] f32 cuda: x, y, maxval per union joint), heatmaps
+    ([nsamples, J, h, w] f32 cuda, or None), u (the annotated union joints, sorted) and meters
+    ({'loss' / 'acc': {'val', 'avg', 'sum', 'count'}}, read once after the last batch)."""
+
+    def __init__(self, perf_indicator, name_values, locations, heatmaps, u, meters):
+        self.perf_indicator = perf_indicator
+        self.name_values = name_values
+        self.locations = locations
+        self.heatmaps = heatmaps
+        self.u = u
+        self.meters = meters
+
+
+def validate_device(config, loader, dataset, model_dict, criterion_dict, output_dir, writer_dict, rank,
+                    keep_heatmaps=True):
+    """function.py:529-690 without debug images, with the epoch on the device.  The predictions (and, with
+    ``keep_heatmaps``, the heatmaps) of every batch go straight into buffers allocated once at
+    len(dataset) * nviews rows; the loss meter (weighted by the batch's images) and the accuracy meter (weighted
+    by the device value cnt) live in a device table that is read only on the ``i % PRINT_FREQ == 0`` line and
+    once after the last batch.  Between two log lines the host only enqueues.
+
+    With ``keep_heatmaps=True`` the end of the loop is ``validate``'s: one copy to the host, the
+    ``heatmaps_locations_<subset>_<type>.h5`` file, ``dataset.evaluate(all_preds[:, u, :], ...)``.  With
+    ``keep_heatmaps=False`` no heatmap is stored and no h5 file is written: only the predictions
+    ([nsamples, J, 3]) are copied for ``dataset.evaluate``.  Returns a ``ValidationResult``;
+    ``result.locations[:, result.u]`` is the cuda ``locations`` tensor that
+    ``multiviews.pseudo_label.pseudo_label_round`` takes."""
+    device = torch.device('cuda', rank)
+    for model in model_dict.values():
+        model.eval()
+    njoints = config.NETWORK.NUM_JOINTS
+    height = int(config.NETWORK.HEATMAP_SIZE[0])
+    width = int(config.NETWORK.HEATMAP_SIZE[1])
+    all_preds = all_heatmaps = None
+    meters = _DeviceMeters(device, names=VALID_METERS)
+    idx = 0
+    end = time.time()
+    for i, (input, target, weight, meta) in enumerate(loader):
+        input = [view.to(device, non_blocking=False) for view in input]
+        if all_preds is None:                        # the epoch buffers, once the number of views is known
+            nsamples = len(dataset) * len(input)
+            all_preds = torch.zeros((nsamples, njoints, 3), dtype=torch.float32, device=device)
+            if keep_heatmaps:
+                all_heatmaps = torch.zeros((nsamples, njoints, height, width), dtype=torch.float32, device=device)
+        r = validate_batch_device(config, model_dict['base_model'], input, target, weight, meta,
+                                  getattr(dataset, 'flip_pairs', None), criterion_dict, all_preds, all_heatmaps, idx)
+        nimgs = r['rows']
+        meters.update({'loss': r['loss'], 'acc': r['acc']}, nimgs, r['cnt'])
+        idx += nimgs
+        if i % config.PRINT_FREQ == 0 and rank == 0:
+            m = meters.read()                        # the one read between two log lines
+            logger.info('Test: [%d/%d]\tTime %.3f\tLoss %.4f (%.4f)\tAccuracy %.3f (%.3f)', i, len(loader),
+                        time.time() - end, m['loss'].val, m['loss'].avg, m['acc'].val, m['acc'].avg)
+        end = time.time()
+    if all_preds is None:                            # an empty loader
+        all_preds = torch.zeros((0, njoints, 3), dtype=torch.float32, device=device)
+        all_heatmaps = torch.zeros((0, njoints, height, width), dtype=torch.float32, device=device) \
+            if keep_heatmaps else None
+    final = {name: {'val': m.val, 'avg': m.avg, 'sum': m.sum, 'count': m.count} for name, m in meters.read().items()}
+    u2a = {k: v for k, v in dataset.u2a_mapping.items() if v != '*'}
+    u = np.array([m[0] for m in sorted(u2a.items(), key=lambda x: x[0])])
+    perf_indicator, name_values = 1000, None
+    if rank == 0:
+        host_preds = all_preds.cpu().numpy()
+        if keep_heatmaps:
+            file_name = os.path.join(output_dir, 'heatmaps_locations_%s_%s.h5' % (dataset.subset, dataset.dataset_type))
+            save_heatmaps_locations(file_name, all_heatmaps.cpu().numpy(), host_preds, u)
+        name_values, perf_indicator = dataset.evaluate(host_preds[:, u, :],
+                                                       output_dir if config.DEBUG.SAVE_ALL_PREDS else None)
+    return ValidationResult(perf_indicator, name_values, all_preds, all_heatmaps, u, final)

@@ -141,6 +141,11 @@ _SIGNATURES = {
     'posu_sample_workspace': [_i],
     'posu_sample_images': [_p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _ll, _p, _p],
     'posu_sample_joints_targets': [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p, _p],
+    # validation epoch (additive to ABI 16)
+    'posu_decode_views_workspace': [_i, _i, _i],
+    'posu_decode_views': [_p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p, _ll, _ll, _p, _p, _p, _p, _p,
+                          _ll, _p],
+    'posu_detection_counts': [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p],
 }
 _RESTYPES = {'posu_last_error': ctypes.c_char_p, 'posu_conv2d_wgrad_workspace': ctypes.c_longlong,
              'posu_pack_job_blocks': ctypes.c_longlong,
@@ -149,7 +154,8 @@ _RESTYPES = {'posu_last_error': ctypes.c_char_p, 'posu_conv2d_wgrad_workspace': 
              'posu_grad_stats_workspace': ctypes.c_longlong, 'posu_heatmap_mi_workspace': ctypes.c_longlong,
              'posu_heatmap_dparams_floats': ctypes.c_longlong, 'posu_pair_mi_workspace': ctypes.c_longlong,
              'posu_pck_accuracy_workspace': ctypes.c_longlong, 'posu_grad_row_norms_workspace': ctypes.c_longlong,
-             'posu_pseudo_label_workspace': ctypes.c_longlong, 'posu_sample_workspace': ctypes.c_longlong}
+             'posu_pseudo_label_workspace': ctypes.c_longlong, 'posu_sample_workspace': ctypes.c_longlong,
+             'posu_decode_views_workspace': ctypes.c_longlong}
 
 
 def library_path():

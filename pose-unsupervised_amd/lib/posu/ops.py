@@ -1165,3 +1165,118 @@ def pckh_counts(pred, vis, gt, head, nviews=1, threshold=0.5, pred_sets=None, se
          ptr(None if head is None else _f64(head.reshape(-1))), b, n, j, int(nviews), float(threshold), ptr(out),
          stream_of(dev))
     return out.view(b, w)
+
+
+# ------------------------------------------------------------ validation epoch
+def decode_views(outputs, flipped=None, perm=None, shift=False, targets=None, affine64=None, post_process=True,
+                 thr=0.5, preds_out=None, merged_out=None, row0=0):
+    """The validation batch body after the forwards for all V views in one launch (posu_decode_views): the
+    flip-test merge 0.5 * (o + flip_back(flipped)) (``perm``: [J] ints, ``shift``: SHIFT_HEATMAP),
+    get_final_preds (``affine64`` [V * N, 2, 3] f64 view-major, ``post_process``) and, with ``targets``, the
+    PCK accuracy of the merged maps.  outputs / flipped / targets: lists of V [N, J, H, W] f32 cuda tensors.
+
+    ``preds_out`` [R, J, 3] f32 (x, y, maxval; allocated at R = V * N when None) and ``merged_out`` [R, J, H, W]
+    f32 (None: the merged maps are not stored) are written at rows row0 + n * V + v, the reference's
+    preds[k::nviews] order; the other rows are left alone.  Returns (preds_out, merged_out, acc [V, J + 1] f64,
+    avg [V] f64, cnt [V] int32, step [2] f64 = the views' mean avg and cnt), the last four None without
+    targets; everything stays on the device and nothing is read back."""
+    import ctypes
+    if not outputs:
+        raise ValueError('decode_views: at least one view expected')
+    outs = _same_maps(outputs, 'decode_views')
+    if outs[0].dim() != 4:
+        raise ValueError('decode_views: [N, J, H, W] outputs expected, got %s' % (tuple(outs[0].shape),))
+    v = len(outs)
+    n, j, h, w = outs[0].shape
+    dev = outs[0].device
+    flips = tgts = None
+    for name, views in (('flipped', flipped), ('targets', targets)):
+        if views is None:
+            continue
+        views = _same_maps(views, 'decode_views')
+        if len(views) != v or views[0].shape != outs[0].shape:
+            raise ValueError('decode_views: one %s tensor of the outputs\' shape per view expected' % name)
+        if name == 'flipped':
+            flips = views
+        else:
+            tgts = views
+    if perm is not None:
+        if flips is None:
+            raise ValueError('decode_views: perm goes with flipped')
+        if not isinstance(perm, torch.Tensor):
+            host = [int(p) for p in perm]
+            if len(host) != j or min(host) < 0 or max(host) >= j:
+                raise ValueError('decode_views: perm must hold J joint indices')
+            perm = torch.tensor(host, dtype=torch.int32)
+        if perm.numel() != j:
+            raise ValueError('decode_views: perm must hold J joint indices')
+        perm = perm.to(device=dev, dtype=torch.int32).contiguous()
+    require_cuda(affine64, preds_out, merged_out)
+    if affine64 is not None:
+        if affine64.numel() != v * n * 6:
+            raise ValueError('decode_views: affine64 must be [V * N, 2, 3], got %s' % (tuple(affine64.shape),))
+        affine64 = affine64.to(device=dev, dtype=torch.float64).contiguous()
+    row0 = int(row0)
+    if preds_out is None:
+        if row0 != 0:
+            raise ValueError('decode_views: row0 needs preds_out')
+        preds_out = torch.empty((v * n, j, 3), dtype=torch.float32, device=dev)
+    rows = preds_out.shape[0]
+    if preds_out.dtype != torch.float32 or tuple(preds_out.shape[1:]) != (j, 3) or not preds_out.is_contiguous():
+        raise ValueError('decode_views: preds_out must be contiguous float32 [R, J, 3]')
+    if merged_out is not None:
+        if merged_out.dtype != torch.float32 or tuple(merged_out.shape[1:]) != (j, h, w) \
+                or not merged_out.is_contiguous():
+            raise ValueError('decode_views: merged_out must be contiguous float32 [R, J, H, W]')
+        rows = min(rows, merged_out.shape[0])
+    ws_bytes = nat.load().posu_decode_views_workspace(v, n, j)
+    if ws_bytes < 0:
+        raise ValueError('decode_views: unsupported shape V=%d N=%d J=%d (1 to 8 views)' % (v, n, j))
+    acc = avg = cnt = step = ws = None
+    if tgts is not None:
+        ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
+        acc = torch.empty((v, j + 1), dtype=torch.float64, device=dev)
+        avg = torch.empty((v,), dtype=torch.float64, device=dev)
+        cnt = torch.empty((v,), dtype=torch.int32, device=dev)
+        step = torch.empty((2,), dtype=torch.float64, device=dev)
+    tables = [None if t is None else _view_pointers(t) for t in (outs, flips, tgts)]
+    po, pf, pt = [None if t is None else ctypes.cast(t, ctypes.c_void_p) for t in tables]
+    call('posu_decode_views', po, pf, ptr(perm), int(bool(shift)), pt, ptr(affine64), v, n, j, h, w,
+         int(bool(post_process)), float(thr), ptr(merged_out), ptr(preds_out), row0, rows, ptr(acc), ptr(avg),
+         ptr(cnt), ptr(step), ptr(ws), ws_bytes, stream_of(dev))
+    return preds_out, merged_out, acc, avg, cnt, step
+
+
+def detection_counts(pred, gt, head, thresholds, form=0, vis=None, out=None):
+    """Per threshold and joint, the rows whose prediction lies within that threshold's head-size distance of the
+    ground truth (posu_detection_counts): pred [N, J, 2] or [N, J, 3] f32 (x, y), gt [N, J, 2], head [N] (or
+    [N, 1]), vis [N, J] (non-zero = counted) or None, all cuda; thresholds: 1 to 8 numbers; form 0: d <= head * thr
+    (the H36M evaluation), form 1: d / head <= thr (the MPII one), in f64 -> counts [T, 2, J] int32 on the device:
+    detected-and-visible and visible."""
+    require_cuda(pred, gt, head, vis, out)
+    if pred.dim() != 3 or pred.shape[2] not in (2, 3):
+        raise ValueError('detection_counts: pred must be [N, J, 2] or [N, J, 3], got %s' % (tuple(pred.shape),))
+    n, j, c = pred.shape
+    if tuple(gt.shape) != (n, j, 2) or head.numel() != n:
+        raise ValueError('detection_counts: gt [N, J, 2] and head [N] expected for pred %s, got %s and %s'
+                         % (tuple(pred.shape), tuple(gt.shape), tuple(head.shape)))
+    if form not in (0, 1):
+        raise ValueError('detection_counts: form 0 (d <= head * thr) or 1 (d / head <= thr), got %r' % (form,))
+    thre = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+    t = int(thre.size)
+    dev = pred.device
+    pred = pred.detach().to(torch.float32).contiguous()
+    if vis is not None:
+        if tuple(vis.shape) != (n, j):
+            raise ValueError('detection_counts: vis must be [N, J], got %s' % (tuple(vis.shape),))
+        vis = vis.detach()
+        if vis.dtype != torch.uint8:
+            vis = vis.ne(0).to(torch.uint8)
+        vis = vis.contiguous()
+    if out is None:
+        out = torch.empty((max(t, 1), 2, j), dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or out.numel() != t * 2 * j or not out.is_contiguous():
+        raise ValueError('detection_counts: out must be contiguous int32 [T, 2, J]')
+    nat.call('posu_detection_counts', ptr(pred), c, ptr(_f64(gt)), ptr(_f64(head.reshape(-1))), ptr(vis), _host(thre),
+             t, int(form), n, j, ptr(out), stream_of(dev))
+    return out.view(t, 2, j)
