@@ -924,6 +924,46 @@ int posu_pair_mi_loss_fwd(const float* u, int S, int N, int Q, int measure, floa
                           long long workspace_bytes, void* stream);
 int posu_pair_mi_loss_bwd(const float* u, int S, int N, int Q, int measure, const float* gloss, float* du,
                           void* stream);
+/* The positions HeatmapMILoss scores, drawn on the device (the reference draws them on the host,
+ * lib/core/loss.py:646-703): per image the window centre, half of the window's entries without
+ * replacement and a quarter as many distinct positions outside it.  Additive to ABI 16.
+ *
+ *   joints: DEVICE f64 [B, J, 2], (x, y) in crop px (meta['joints_2d_transformed']);
+ *   vis:    DEVICE f64 [B, J], joint visible when != 0 (column 0 of meta['joints_vis']);
+ *   feat_w, feat_h: crop px per map px; the map is H x W; the window is (2 radius + 1)^2;
+ *   idx:    DEVICE int32 [B, Q] out; loc: DEVICE int32 [B] out, the window centres, may be NULL.
+ * With P = (2 radius + 1)^2, n_in = P / 2, n_out = P / 4 (integer divisions), Q = n_in + n_out.
+ *
+ * The stream.  Row k's draw is a function of (seed, call, k) and of row k's inputs only: not of B,
+ * of the launch geometry or of other rows, so a batch may be drawn in one launch or in pieces.  Its
+ * random words are the outputs of Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants
+ * 0x9E3779B9, 0xBB67AE85) with key (seed low 32 bits, seed high 32 bits) and counter (b, k, call
+ * low, call high) for b = 0, 1, 2, ..., consumed in output order.  bounded(w, n) = (w * n) >> 32 on
+ * the 64-bit product maps a word to [0, n); the relative bias of an outcome is at most n / 2^32:
+ * below 2.5e-7 for the window draws (n <= 1024) and for the 64 x 64 map (none at all when n is a
+ * power of two), at most 1.6e-5 for the largest map allowed here.
+ *   centre: gx = trunc(joints[k, joint_idx, 0] / feat_w + 0.5) in f64 (IEEE division, truncation
+ *     toward zero) clamped to [0, W - 1] (NaN gives 0), gy likewise with feat_h and H, gt = gy W +
+ *     gx: HeatmapMILoss.locations' integers for finite coordinates below 2^31.  Word 0 is always
+ *     consumed: centre = visible ? gt : bounded(w0, H W) (the reference's uniform centre for an
+ *     invisible joint, loss.py:698; image k keeps slot k);
+ *   window: entry e = (dy + radius)(2 radius + 1) + (dx + radius) holds clamp(centre + dy W + dx, 0,
+ *     H W - 1): the LINEAR index is clamped (loss.py:654-657), so a window at a border repeats
+ *     positions;
+ *   inside: a partial Fisher-Yates over the P entries: perm = identity; for t = 0 .. n_in - 1:
+ *     j = t + bounded(next word, P - t), swap perm[t] and perm[j], idx[k, t] = window[perm[t]];
+ *   outside: p = bounded(next word, H W) repeatedly, accepted when it is neither a window position
+ *     nor already accepted; idx[k, n_in + a] = the a-th accepted p.  After 64 n_out draws the
+ *     remaining slots take the lowest free positions in ascending order (the limits keep the
+ *     acceptance above 1/2, so this is unreachable in practice; it bounds the loop);
+ *   loc[k] = centre.
+ * Limits (POSU_ERR_ARG before any launch): non-null joints, vis, idx; joint_idx in [0, J);
+ * radius >= 1; P <= 1024; H W <= 65536; P + P / 4 <= H W / 2; feat_w, feat_h finite and positive.
+ * B == 0 succeeds without a launch.  `call` is a by-value argument: a captured graph would replay
+ * one draw. */
+int posu_heatmap_mi_sample(const double* joints, const double* vis, int B, int J, int joint_idx, double feat_w,
+                           double feat_h, int H, int W, int radius, unsigned long long seed,
+                           unsigned long long call, int* idx, int* loc, void* stream);
 
 /* ------------------------------------------------- training-loop metrics */
 /* What lib/core/function.py:91-527 (train) computes about a step besides the losses, without a

@@ -120,11 +120,26 @@ JointsMILoss = _not_built('JointsMILoss', 'only HeatmapMILoss is built')
 class HeatmapMILoss:
     """Reference lib/core/loss.py:636-781.  Constructor and ``__call__`` are the reference's (one
     view in, the scalar loss out); ``sample_indices`` exposes the position sampling, ``indices=``
-    takes positions drawn elsewhere, and ``views`` sums the loss over a list of views in one call."""
+    takes positions drawn elsewhere, and ``views`` sums the loss over a list of views in one call.
+
+    sampler='host' (the default) draws the positions with torch on the host, like the reference; it reads
+    the two meta entries, which is a synchronisation when they live on the device.  sampler='device'
+    draws them with a counter-based kernel (``sample_indices_device``) from `seed` (None: one value from
+    torch's default generator at construction) and the number of draws made so far, and nothing between
+    the metadata and the loss touches the host.  ``sampler_state`` / ``load_sampler_state`` carry
+    {'seed', 'calls'} through a checkpoint.  DDP ranks need different seeds (a caller who passes `seed`
+    adds the rank).  The sampling is not graph-capturable: the call number is a by-value argument."""
 
     MAP = 64   # the reference asserts 64 x 64 low-level and heatmap maps (loss.py:686, 714-716)
 
-    def __init__(self, cfg, discriminator_dict):
+    def __init__(self, cfg, discriminator_dict, sampler='host', seed=None):
+        if sampler not in ('host', 'device'):
+            raise ValueError("HeatmapMILoss sampler must be 'host' or 'device', got %r" % (sampler,))
+        self.sampler = sampler
+        self._seed, self._calls = None, 0
+        if sampler == 'device':
+            # one 63-bit value from torch's default host generator, so torch.manual_seed repeats a run
+            self._seed = int(seed) if seed is not None else int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
         self.use_target_weight = cfg.LOSS.USE_TARGET_WEIGHT
         self.measure = cfg.LOSS.HEATMAP_MI_MEASURE
         if self.measure not in ops.MI_MEASURES:
@@ -173,6 +188,43 @@ class HeatmapMILoss:
         idx = torch.cat([inside, outside], dim=1)
         return (idx, loc) if return_locations else idx
 
+    # -- sampling on the device (posu_heatmap_mi_sample, include/posu.h)
+    def sample_indices_device(self, meta, joint_idx, return_locations=False):
+        """sample_indices on the device, for one meta dict ([N, Q] int32 cuda) or a list of them (one launch
+        over the concatenated rows, view-major: [V N, Q], row k = v N + n).  The metadata may live on the
+        host or on the device; it is uploaded, never read back.  Every launch uses call number
+        ``self._calls`` and then increments it, and row k's draw depends on (seed, call, k) alone, so a
+        seed and a call count name the whole sequence (``sampler_state``).  Under DDP every rank needs its
+        own seed: ``seed=None`` draws it from the rank's torch generator, a caller who passes ``seed`` adds
+        the rank.  The call number is a by-value kernel argument, so the sampling cannot be captured in a
+        graph (a replay would repeat one draw)."""
+        if self.sampler != 'device':
+            raise RuntimeError("sample_indices_device needs HeatmapMILoss(..., sampler='device')")
+        metas = [meta] if isinstance(meta, dict) else list(meta)
+        joints = [torch.as_tensor(m['joints_2d_transformed']) for m in metas]
+        vis = [torch.as_tensor(m['joints_vis']) for m in metas]
+        dev = next((t.device for t in joints + vis if t.is_cuda), None)
+        if dev is None:
+            if not torch.cuda.is_available():
+                ops.require_cuda(*joints)    # no GPU: the library's refusal, never a host fallback
+            dev = torch.device('cuda', torch.cuda.current_device())
+        vis = [v[:, :, 0] if v.dim() == 3 else v for v in vis]
+        joints = torch.cat([t.to(device=dev, dtype=torch.float64) for t in joints], dim=0)
+        vis = torch.cat([t.to(device=dev, dtype=torch.float64) for t in vis], dim=0)
+        idx, loc = ops.heatmap_mi_sample(joints, vis, joint_idx, (float(self.feat[0]), float(self.feat[1])),
+                                         (self.MAP, self.MAP), int(self.sigma * 3 + 2), self._seed, self._calls)
+        self._calls += 1
+        return (idx, loc) if return_locations else idx
+
+    def sampler_state(self):
+        """{'seed', 'calls'} of the device sampler, for a checkpoint."""
+        return {'seed': self._seed, 'calls': self._calls}
+
+    def load_sampler_state(self, state):
+        if self.sampler != 'device':
+            raise RuntimeError("load_sampler_state needs HeatmapMILoss(..., sampler='device')")
+        self._seed, self._calls = int(state['seed']), int(state['calls'])
+
     def _check_maps(self, low_features, high_features):
         if tuple(low_features.shape[2:]) != (self.MAP, self.MAP) or tuple(high_features.shape[2:]) != (self.MAP,
                                                                                                       self.MAP):
@@ -180,24 +232,35 @@ class HeatmapMILoss:
                                       % (tuple(low_features.shape[2:]), tuple(high_features.shape[2:])))
 
     def __call__(self, low_features, high_features, target_weight, meta, joint_idx, indices=None):
-        """low_features [N, C, 64, 64], high_features [N, J, 64, 64] (cuda), meta on the host."""
+        """low_features [N, C, 64, 64], high_features [N, J, 64, 64] (cuda), meta on the host (with
+        sampler='device': on the host or on the device, and `indices` may be a cuda tensor)."""
         self._check_maps(low_features, high_features)
         if indices is None:
-            indices = self.sample_indices(meta, joint_idx)
+            indices = (self.sample_indices_device(meta, joint_idx) if self.sampler == 'device'
+                       else self.sample_indices(meta, joint_idx))
         u = self.heatmap_d.pair_scores(low_features, high_features, indices, joint_idx, nseg=1)
         return ops.pair_mi_loss(u, self.measure, 1)[0]
 
     def views(self, low_list, out_list, weight_list, meta_list, joint_idx, indices=None):
         """sum over views of __call__ (function.py:266-267 / 276-277) as one call: the views are
         the segments of the kernels, each with its own BatchNorm statistics, and the running
-        buffers end as after the per-view calls in order.  indices: None or one [N, Q] per view."""
+        buffers end as after the per-view calls in order.  indices: None or one [N, Q] per view; with
+        sampler='device' the positions of all views are drawn in one launch, and `indices` may also be
+        cuda tensors (one [N, Q] per view or one [V N, Q]), which never leave the device."""
         nseg = len(low_list)
         for l, o in zip(low_list, out_list):
             self._check_maps(l, o)
-        if indices is None:
+        if indices is None and self.sampler == 'device':
+            indices = self.sample_indices_device(list(meta_list), joint_idx)   # all views in one launch
+        elif indices is None:
             indices = [self.sample_indices(m, joint_idx) for m in meta_list]
         low = low_list[0] if nseg == 1 else torch.cat(list(low_list), dim=0)
         out = out_list[0] if nseg == 1 else torch.cat(list(out_list), dim=0)
-        idx = torch.cat([torch.as_tensor(i).cpu() for i in indices], dim=0)
+        if self.sampler == 'device' and isinstance(indices, torch.Tensor):
+            idx = indices                                          # one [V N, Q], host or device
+        elif self.sampler == 'device' and all(isinstance(i, torch.Tensor) and i.is_cuda for i in indices):
+            idx = torch.cat(list(indices), dim=0)                  # stays on the device
+        else:
+            idx = torch.cat([torch.as_tensor(i).cpu() for i in indices], dim=0)
         u = self.heatmap_d.pair_scores(low, out, idx, joint_idx, nseg=nseg)
         return ops.pair_mi_loss(u, self.measure, nseg).sum()

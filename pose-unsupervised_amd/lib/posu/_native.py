@@ -29,6 +29,7 @@ _i = ctypes.c_int
 _f = ctypes.c_float
 _ll = ctypes.c_longlong
 _d = ctypes.c_double
+_ull = ctypes.c_ulonglong
 
 # name -> argtypes (restype is int unless listed in _RESTYPES)
 _SIGNATURES = {
@@ -123,6 +124,7 @@ _SIGNATURES = {
     'posu_pair_mi_workspace': [_i],
     'posu_pair_mi_loss_fwd': [_p, _i, _i, _i, _i, _p, _p, _ll, _p],
     'posu_pair_mi_loss_bwd': [_p, _i, _i, _i, _i, _p, _p, _p],
+    'posu_heatmap_mi_sample': [_p, _p, _i, _i, _i, _d, _d, _i, _i, _i, _ull, _ull, _p, _p, _p],
     # training-loop metrics (additive to ABI 16)
     'posu_pck_accuracy_workspace': [_i, _i, _i],
     'posu_pck_accuracy': [_p, _p, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p, _p, _p, _ll, _p],

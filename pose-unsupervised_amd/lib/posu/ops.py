@@ -797,10 +797,15 @@ def _mi_geometry(feat, hm, idx, p):
     return b, h, w, c, hm.shape[1], q, cm
 
 
+def _host_ptr(a):
+    return None if a is None else a.ctypes.data
+
+
 class _HeatmapPairScores(torch.autograd.Function):
     """u[n, i, j] of the discriminator over (feature row idx[n, i], heatmap value idx[n, j]).
     feat: [B, H, W, C] contiguous (f32 / bf16 / f16); hm: [B, J, H, W] f32; idx: [B, Q] int32 on the
-    device, idx_host its host copy (checked by the library).  Returns (u, stats)."""
+    device, idx_host its host copy (checked by the library) or None (indices made on the device: the range
+    is then the caller's contract and the kernels clamp).  Returns (u, stats)."""
 
     @staticmethod
     def forward(ctx, feat, hm, idx, idx_host, joint_idx, nseg, training, eps, *params):
@@ -814,7 +819,7 @@ class _HeatmapPairScores(torch.autograd.Function):
         u = torch.empty((b, q, q), dtype=torch.float32, device=feat.device)
         tab = _mi_param_table(p, training)
         call('posu_heatmap_pair_scores_fwd', nat.dtype_code_of(feat), ptr(feat), ptr(hm), nseg, n, h, w, c, j,
-             int(joint_idx), ptr(idx), idx_host.ctypes.data, q, cm, tab, int(training), float(eps), ptr(stats), ptr(u),
+             int(joint_idx), ptr(idx), _host_ptr(idx_host), q, cm, tab, int(training), float(eps), ptr(stats), ptr(u),
              ptr(ws), ws_bytes, stream_of(feat.device))
         # training mode normalises with batch statistics: the running buffers (updated in place by
         # the module after this call) are not part of the backward
@@ -850,7 +855,7 @@ class _HeatmapPairScores(torch.autograd.Function):
         du = du.contiguous().float()
         tab = _mi_param_table(p, ctx.training)
         call('posu_heatmap_pair_scores_bwd', nat.dtype_code_of(feat), ptr(feat), ptr(hm), nseg, n, h, w, c, j,
-             ctx.joint_idx, ptr(idx), ctx.idx_host.ctypes.data, q, cm, tab, int(ctx.training), float(ctx.eps),
+             ctx.joint_idx, ptr(idx), _host_ptr(ctx.idx_host), q, cm, tab, int(ctx.training), float(ctx.eps),
              ptr(stats), ptr(du), ptr(dparams), ptr(dfeat), ptr(dhm), ptr(ws), ws_bytes, stream_of(dev))
         out[0], out[1] = dfeat, dhm
         if want_params:
@@ -871,8 +876,10 @@ def heatmap_pair_scores(low_features, heatmaps, indices, joint_idx, params, nseg
 
     low_features [B, C, H, W] (f32 / bf16 / f16): a tensor whose channel stride is 1 (the backbone's
     x1.permute(0, 3, 1, 2)) is read in place, anything else is made channels-last once.
-    heatmaps [B, J, H, W]; indices [B, Q] integer (host or device); B = nseg * N, statistics per
-    segment.  params: dict of W1, g1, be1, rm1, rv1, W2, b2, g2, be2, rm2, rv2, w3, b3 (f32)."""
+    heatmaps [B, J, H, W]; indices [B, Q] integer; B = nseg * N, statistics per segment.  Host indices are
+    range-checked by the library; an int32 / int64 cuda tensor is used in place (converted to int32 on the
+    device if need be) with no copy to the host: its range is the caller's contract, the kernels clamp.
+    params: dict of W1, g1, be1, rm1, rv1, W2, b2, g2, be2, rm2, rv2, w3, b3 (f32)."""
     require_cuda(low_features, heatmaps, *[t for t in params.values() if t is not None])
     if low_features.dtype not in (torch.float32, torch.bfloat16, torch.float16):
         low_features = low_features.float()
@@ -882,13 +889,50 @@ def heatmap_pair_scores(low_features, heatmaps, indices, joint_idx, params, nseg
     if feat.shape[0] % nseg:
         raise ValueError('heatmap MI: %d images do not split into %d segments' % (feat.shape[0], nseg))
     hm = heatmaps.contiguous().float()
-    idx_host = np.ascontiguousarray(indices.detach().cpu().numpy().astype(np.int32))
-    idx = torch.from_numpy(idx_host).to(feat.device)
+    if isinstance(indices, torch.Tensor) and indices.is_cuda and indices.dtype in (torch.int32, torch.int64):
+        # made on the device (heatmap_mi_sample): used in place, never copied to the host to be checked
+        idx_host = None
+        idx = indices.detach().to(device=feat.device, dtype=torch.int32).contiguous()
+    else:
+        idx_host = np.ascontiguousarray(indices.detach().cpu().numpy().astype(np.int32))
+        idx = torch.from_numpy(idx_host).to(feat.device)
     plist = []
     for name in _MI_PARAMS:
         t = params[name]
         plist.append(None if t is None else t.contiguous().float())
     return _HeatmapPairScores.apply(feat, hm, idx, idx_host, joint_idx, nseg, bool(training), eps, *plist)
+
+
+def heatmap_mi_sample(joints, vis, joint_idx, feat, map_hw, radius, seed, call):
+    """The positions HeatmapMILoss scores, drawn on the device (posu_heatmap_mi_sample; include/posu.h
+    defines the stream): (idx [B, Q] int32, loc [B] int32, the window centres), Q = P // 2 + P // 4 for
+    P = (2 radius + 1)^2.  Row k depends on (seed, call, k) and on its own inputs only.
+
+    joints [B, J, 2] crop px and vis [B, J] or [B, J, k] (column 0 is used): host or device tensors of any
+    float dtype, brought to f64 on the device (an upload, never a read).  feat: crop px per map px (w, h);
+    map_hw: (H, W).  `call` is passed by value, so a captured graph would replay one draw."""
+    joints, vis = torch.as_tensor(joints), torch.as_tensor(vis)
+    dev = joints.device if joints.is_cuda else (vis.device if vis.is_cuda else None)
+    if dev is None:
+        if not torch.cuda.is_available():
+            require_cuda(joints, vis)
+        dev = torch.device('cuda', torch.cuda.current_device())
+    if vis.dim() == 3:
+        vis = vis[:, :, 0]
+    if joints.dim() != 3 or joints.shape[2] != 2 or tuple(vis.shape) != tuple(joints.shape[:2]):
+        raise ValueError('heatmap_mi_sample: joints [B, J, 2] and vis [B, J] or [B, J, k] expected, got %s and %s'
+                         % (tuple(joints.shape), tuple(vis.shape)))
+    joints = joints.detach().to(device=dev, dtype=torch.float64).contiguous()
+    vis = vis.detach().to(device=dev, dtype=torch.float64).contiguous()
+    b, j = vis.shape
+    p = (2 * int(radius) + 1) ** 2
+    idx = torch.empty((b, p // 2 + p // 4), dtype=torch.int32, device=dev)
+    loc = torch.empty((b,), dtype=torch.int32, device=dev)
+    if b:   # (`call` the argument shadows the binding's call here)
+        nat.call('posu_heatmap_mi_sample', ptr(joints), ptr(vis), b, j, int(joint_idx), float(feat[0]),
+                 float(feat[1]), int(map_hw[0]), int(map_hw[1]), int(radius), int(seed), int(call), ptr(idx),
+                 ptr(loc), stream_of(dev))
+    return idx, loc
 
 
 class _PairMILoss(torch.autograd.Function):
