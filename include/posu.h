@@ -1094,6 +1094,51 @@ int posu_pckh_counts(const double* pred, const double* pred_sets, const int* set
                      const unsigned char* vis, const double* gt, const double* head, int B, int N, int J,
                      int V, double threshold, int* counts, void* stream);
 
+/* ---------------------------------------------------- fundamental matrices */
+/* The table FundamentalLoss reads, estimated from 2-D correspondences (the reference makes it with
+ * cv2.findFundamentalMat(pts_i, pts_j, cv2.FM_LMEDS), run/test/generate_fundamental_matirx.py:36-103): a
+ * least-median-of-squares estimator over the normalised 8-point algorithm for P independent problems
+ * (one per subject and view pair) in one call (csrc/fundamental.hip).  Additive to ABI 16.  fp64,
+ * stream-ordered, no allocation, no host read; the same inputs and seed give the same bits.
+ *   pts:   [P, N, 4] f64, (x_i, y_i, x_j, y_j) in pixels;  valid: NULL (every row) or [P, N] uint8;
+ *   H hypotheses per problem;  n = the problem's valid rows.
+ * Hypothesis h of problem p:
+ *   sample  8 distinct valid rows.  The words are those of the Philox4x32-10 blocks (see
+ *           posu_heatmap_mi_sample) with key (seed low, seed high) and counter (b, h, p, 0), b = 0, 1, ...,
+ *           consumed in output order; a word gives the candidate row (word * N) >> 32, rejected when the
+ *           row is invalid or already taken.  The 64th rejection ends the hypothesis: it is unusable and
+ *           its median is +inf.  The 8 rows are then sorted ascending, so that two hypotheses with the
+ *           same rows are the same hypothesis bit for bit.
+ *   solve   Hartley normalisation of each image's 8 points (centroid to the origin, mean distance
+ *           sqrt 2); the 8 x 9 system with rows [xj xi, xj yi, xj, yj xi, yj yi, yj, xi, yi, 1], i.e.
+ *           x_j^T F x_i = 0; the right singular vector of the smallest singular value by one-sided Jacobi;
+ *           rank 2 by a 3 x 3 Jacobi SVD with the smallest singular value set to zero; F = T_j^T F^ T_i.
+ *   score   a valid row's error is max(d_i^2, d_j^2), the squared distances of x_i to the line F^T x_j
+ *           and of x_j to the line F x_i; a NaN counts as +inf.  The hypothesis's median is the exact
+ *           element of rank n / 2 (0-based, integer division) of these errors.  N has no cap.
+ * Per problem: the winner is the smallest median (ties to the lowest h);
+ *   sigma = 2.5 * 1.4826 * (1 + 5 / (n - 8)) * sqrt(median), the 5 / (n - 8) taken as 0 for n = 8,
+ *   floored at 1e-3 px; the inliers are the valid rows with error <= sigma^2; with refit != 0 the
+ *   normalised 8-point solve is repeated over all inliers on the 9 x 9 Gram matrix of their rows, else
+ *   the winner itself is kept; the result is scaled to F[2][2] = 1, or to Frobenius norm 1 when
+ *   |F[2][2]| <= 1e-7 max|F|.  A problem with n < 8, without a usable hypothesis, with fewer than 8
+ *   inliers or with a non-finite result writes a zero matrix, a zero mask and n_inliers = 0.
+ *   F: [P, 3, 3] f64;  mask: [P, N] uint8;  sample: [P, 8] int32, the winner's rows (-1 without one);
+ *   stats: [P, 4] f64: the winning median (+inf without a winner), sigma, n_inliers, the winning h (-1);
+ *   workspace: DEVICE, 8-byte aligned, at least posu_fundamental_workspace(P, N, H) bytes, which answers
+ *   on the host (-1 outside 1 <= P <= 65535, 8 <= N <= 2^26, 1 <= H <= 2^20).
+ * POSU_ERR_ARG before any launch: a null pointer (valid excepted), P < 1, N < 8, H < 1, a workspace that
+ * is too small. */
+long long posu_fundamental_workspace(int P, int N, int H);
+int posu_fundamental_lmeds(const double* pts, const unsigned char* valid, int P, int N, int H,
+                           unsigned long long seed, int refit, double* F, unsigned char* mask, int* sample,
+                           double* stats, void* workspace, long long workspace_bytes, void* stream);
+/* The check the generator prints (:54-63): per problem the mean and the max over the valid rows of
+ * |x_j^T F x_i|.  F: [P, 3, 3] f64; pts, valid as above (N >= 1); out: [P, 2] f64 (mean, max; zeros
+ * without a valid row). */
+int posu_epipolar_residual_stats(const double* F, const double* pts, const unsigned char* valid, int P, int N,
+                                 double* out, void* stream);
+
 /* ------------------------------------------------------- validation epoch */
 /* The batch body of validate (lib/core/function.py:529-690) after the forwards, for all V (1..8) views
  * in one launch (csrc/validate.hip), additive to ABI 16.  One wave per map (v, n, j).  Stream-ordered,

@@ -1324,3 +1324,61 @@ def detection_counts(pred, gt, head, thresholds, form=0, vis=None, out=None):
     nat.call('posu_detection_counts', ptr(pred), c, ptr(_f64(gt)), ptr(_f64(head.reshape(-1))), ptr(vis), _host(thre),
              t, int(form), n, j, ptr(out), stream_of(dev))
     return out.view(t, 2, j)
+
+
+def _valid_u8(valid, shape, what):
+    if valid is None:
+        return None
+    if tuple(valid.shape) != tuple(shape):
+        raise ValueError('%s: valid must be %s, got %s' % (what, list(shape), tuple(valid.shape)))
+    valid = valid.detach()
+    if valid.dtype != torch.uint8:
+        valid = valid.ne(0).to(torch.uint8)
+    return valid.contiguous()
+
+
+def fundamental_workspace(p, n, h):
+    """Bytes of posu_fundamental_lmeds' device workspace; raises ValueError for shapes it refuses."""
+    nbytes = nat.load().posu_fundamental_workspace(int(p), int(n), int(h))
+    if nbytes < 0:
+        raise ValueError('fundamental_workspace: 1 <= P <= 65535, 8 <= N <= 2^26, 1 <= H <= 2^20 expected, got P=%d '
+                         'N=%d H=%d' % (p, n, h))
+    return nbytes
+
+
+def fundamental_lmeds(pts, valid=None, hypotheses=512, seed=0, refit=True):
+    """Least-median-of-squares fundamental matrices of P problems in one call (posu_fundamental_lmeds;
+    include/posu.h defines the estimator): pts [P, N, 4] (x_i, y_i, x_j, y_j) px, valid [P, N] or None, cuda ->
+    (F [P, 3, 3] f64, mask [P, N] uint8, sample [P, 8] int32, stats [P, 4] f64: median, sigma, n_inliers, the
+    winning hypothesis), all on the device."""
+    require_cuda(pts, valid)
+    if pts.dim() != 3 or pts.shape[2] != 4:
+        raise ValueError('fundamental_lmeds: pts must be [P, N, 4], got %s' % (tuple(pts.shape),))
+    p, n, _ = pts.shape
+    nbytes = fundamental_workspace(p, n, hypotheses)
+    dev = pts.device
+    pts = _f64(pts)
+    valid = _valid_u8(valid, (p, n), 'fundamental_lmeds')
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    F = torch.empty((p, 3, 3), dtype=torch.float64, device=dev)
+    mask = torch.empty((p, n), dtype=torch.uint8, device=dev)
+    sample = torch.empty((p, 8), dtype=torch.int32, device=dev)
+    stats = torch.empty((p, 4), dtype=torch.float64, device=dev)
+    nat.call('posu_fundamental_lmeds', ptr(pts), ptr(valid), p, n, int(hypotheses), int(seed) & (2 ** 64 - 1),
+             int(bool(refit)), ptr(F), ptr(mask), ptr(sample), ptr(stats), ptr(ws), nbytes, stream_of(dev))
+    return F, mask, sample, stats
+
+
+def epipolar_residual_stats(F, pts, valid=None):
+    """Per problem the mean and the max over the valid rows of |x_j^T F x_i| (posu_epipolar_residual_stats):
+    F [P, 3, 3], pts [P, N, 4], valid [P, N] or None, cuda -> [P, 2] f64 on the device."""
+    require_cuda(F, pts, valid)
+    if pts.dim() != 3 or pts.shape[2] != 4 or tuple(F.shape) != (pts.shape[0], 3, 3):
+        raise ValueError('epipolar_residual_stats: F [P, 3, 3] and pts [P, N, 4] expected, got %s and %s'
+                         % (tuple(F.shape), tuple(pts.shape)))
+    p, n, _ = pts.shape
+    valid = _valid_u8(valid, (p, n), 'epipolar_residual_stats')
+    out = torch.empty((p, 2), dtype=torch.float64, device=pts.device)
+    nat.call('posu_epipolar_residual_stats', ptr(_f64(F)), ptr(_f64(pts)), ptr(valid), p, n, ptr(out),
+             stream_of(pts.device))
+    return out
