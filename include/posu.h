@@ -607,6 +607,52 @@ int posu_reproject(const double* M, const double* intr, const double* xy, const 
                    int G, int V, int J, int undistort, double* proj, unsigned char* res_vis,
                    void* stream);
 
+/* Differentiable triangulation and the reprojection-consistency loss (additive to ABI 16; csrc/
+ * triangulate_grad.hip).  One thread per (group, joint), fp64, 2 <= V <= 4, no atomics: the same inputs give
+ * the same bits.  M, intr, xy (with xy_dtype and the two strides, view-major included), vis and undistort are
+ * posu_triangulate_dlt's.  All of them return POSU_ERR_ARG before any launch for a null required pointer, V
+ * outside 2..4 or another xy dtype, and succeed without a launch when G == 0.
+ *
+ * posu_triangulate_dlt_w: posu_triangulate_dlt with w: NULL (then it IS posu_triangulate_dlt, bit for bit) or
+ * [G, V, J] f64 row weights: the two DLT rows of view v are multiplied by w[g][v][k] (a confidence).
+ *   X: [G, J, 3] f64; (0, 0, 0) for a joint seen in fewer than two views. */
+int posu_triangulate_dlt_w(const double* M, const double* intr, const void* xy, int xy_dtype,
+                           int xy_stride_g, int xy_stride_v, const unsigned char* vis, const double* w,
+                           int G, int V, int J, int undistort, double* X, void* stream);
+/* Its backward from gX [G, J, 3] f64; the forward is recomputed from the same inputs.  With A the weighted
+ * 2V x 4 system, A^T A = sum lam_i q_i q_i^T, h = q_min, X = h[:3] / h[3]:
+ *   gh = (gX / h3, -(gX . X) / h3),  z = sum_{i != min} q_i (q_i . gh) / (lam_min - lam_i),
+ *   gA = (A z) h^T + (A h) z^T;  the row w (u m2 - m0) gives g_u = w (gA_row . m2), g_w += gA_row . (u m2 - m0);
+ * g_u, g_v then go through the 2 x 2 Jacobian of the five undistortion iterations as they are computed.
+ *   gxy: xy's dtype and layout (every entry of the V views is written: zero for a view that is off and for a
+ *        joint seen in fewer than two views);  gw: NULL or [G, V, J] f64 (written likewise). */
+int posu_triangulate_dlt_bwd(const double* M, const double* intr, const void* xy, int xy_dtype,
+                             int xy_stride_g, int xy_stride_v, const unsigned char* vis, const double* w,
+                             int G, int V, int J, int undistort, const double* gX, void* gxy, double* gw,
+                             void* stream);
+/* Reprojection loss: per (g, k) the point X of posu_triangulate_dlt_w is projected into every view with the
+ * lens model of intr (as posu_reproject does), e[g][v][k] = ||proj - xy[g][v][k]|| in px, and
+ *   loss = sum omega e / (G V J)         (the constant divisor, as posu_epipolar_loss_fwd has it)
+ * with omega NULL (1) or [G, V, J] f64 residual weights, forced to 0 where the view is off or the joint is seen
+ * in fewer than two views.  loss: [1] f64 (written, not accumulated; untouched when G == 0).
+ * X: NULL or [G, J, 3] f64; e: NULL or [G, V, J] f64 (0 for a joint seen in fewer than two views).
+ * workspace: posu_reprojection_loss_workspace(G, J) bytes (-1: bad shape), 8-byte aligned: one partial sum per
+ * 256 (group, joint)s, summed in a fixed order by a second launch. */
+long long posu_reprojection_loss_workspace(int G, int J);
+int posu_reprojection_loss_fwd(const double* M, const double* intr, const void* xy, int xy_dtype,
+                               int xy_stride_g, int xy_stride_v, const unsigned char* vis, const double* w,
+                               const double* omega, int G, int V, int J, int undistort, double* loss,
+                               double* X, double* e, void* workspace, long long workspace_bytes, void* stream);
+/* d loss / d xy and d loss / d w from the device scalar gloss [1] f64.  detach_point == 0: the gradient reaches
+ * xy directly (-omega r / ||r||, r = proj - xy) and through X (the projection's Jacobian, then
+ * posu_triangulate_dlt_bwd's path), and reaches w through X.  detach_point != 0: X is a constant (the online
+ * pseudo-label reading), only the direct term remains and gw is zero.  r = 0 contributes zero, never NaN.
+ *   gxy: xy's dtype and layout;  gw: NULL or [G, V, J] f64. */
+int posu_reprojection_loss_bwd(const double* M, const double* intr, const void* xy, int xy_dtype,
+                               int xy_stride_g, int xy_stride_v, const unsigned char* vis, const double* w,
+                               const double* omega, int G, int V, int J, int undistort, int detach_point,
+                               const double* gloss, void* gxy, double* gw, void* stream);
+
 /* ------------------------------------------------------------------- RPSM */
 /* The recursive pictorial structure model (lib/multiviews/pictorial.py, driven by
  * run/test/test_rpsm.py): multi-view heatmaps -> 3-D pose by max-product inference over the

@@ -9,6 +9,10 @@
   B x 12 small matmuls from a Python loop) + its backward.  The fundamental matrices
   are read from ``<DATASET.ROOT>/testdata/fundamental_matrix.pkl`` like the reference
   ({(subject, i, j): 3x3}), or given directly as a dict.
+* ReprojectionLoss (no reference counterpart): its n-view sibling.  All views are triangulated (fp64 DLT,
+  optionally confidence-weighted), the point is projected back into every view and the pixel distance to
+  the predictions is the loss; the backward goes through the projection, the smallest singular vector and
+  the undistortion (csrc/triangulate_grad.hip).
 
 * HeatmapMILoss (loss.py:636-781): the mutual information (JSD or InfoNCE) between the
   sampled heatmap values of one joint and the backbone's low-level feature rows, scored by
@@ -103,6 +107,79 @@ class FundamentalLoss:
         if self.use_target_weight:
             w = torch.stack([t.reshape(batch_size, -1) for t in target_weight], dim=0)
         return ops.epipolar_loss(x, w, self.F, self.subject_indices(subject))
+
+
+class ReprojectionLoss:
+    """The n-view counterpart of FundamentalLoss (no reference counterpart: the quantity the pseudo-label
+    round computes offline as its reprojected labels, as a loss): the predictions of all views are
+    triangulated, the point is projected back into every view with the lens model, and the pixel distance
+    to the predictions is averaged (ops.reprojection_loss; 2 to 4 views).
+
+    camera_dict: {(subject, view): camera dict in the H36M layout}; it becomes the [S, V, 3, 4] / [S, V, 9]
+    device tables of multiviews.triangulate.camera_table (DATASET.NO_DISTORTION honoured), gathered per
+    sample by meta[0]['subject'] on the device."""
+
+    def __init__(self, cfg, camera_dict, device=None):
+        from multiviews.triangulate import camera_table
+        self.use_target_weight = getattr(cfg.LOSS, 'USE_TARGET_WEIGHT_REPROJ', True)
+        self.no_distortion = bool(getattr(cfg.DATASET, 'NO_DISTORTION', False))
+        if device is None:
+            if torch.distributed.is_available() and torch.distributed.is_initialized():
+                device = torch.device('cuda', torch.distributed.get_rank() % max(torch.cuda.device_count(), 1))
+            else:
+                device = torch.device('cuda', torch.cuda.current_device())
+        self.device = device
+        keys = list(camera_dict.keys())
+        self.subjects = sorted({k[0] for k in keys})
+        self.nviews = 1 + max(k[1] for k in keys)
+        M = np.zeros((len(self.subjects), self.nviews, 3, 4))
+        intr = np.zeros((len(self.subjects), self.nviews, 9))
+        self._missing = {}  # subject -> first (subject, view) key absent from the dict
+        for si, s in enumerate(self.subjects):
+            for v in range(self.nviews):
+                if (s, v) in camera_dict:
+                    M[si, v], intr[si, v] = camera_table(camera_dict[(s, v)], self.no_distortion)
+                else:
+                    self._missing.setdefault(s, (s, v))
+        self.M = torch.from_numpy(M).to(device)
+        self.intr = torch.from_numpy(intr).to(device)
+        self._subj_index = {s: i for i, s in enumerate(self.subjects)}
+
+    def subject_indices(self, subjects):
+        """Rows of the camera tables; a subject without cameras, or with a (subject, view) missing from the
+        dict, raises KeyError like FundamentalLoss.subject_indices -- never a silent zero camera."""
+        subjects = np.asarray(subjects).tolist()
+        for s in subjects:
+            if s in self._missing:
+                raise KeyError(self._missing[s])
+            if s not in self._subj_index:
+                raise KeyError((s, 0))
+        idx = np.array([self._subj_index[s] for s in subjects], dtype=np.int64)
+        return torch.from_numpy(idx).to(self.device)
+
+    def __call__(self, joints_2d_list, target_weight, meta, confidence=None, detach_point=False):
+        """joints_2d_list: V x [K, J, 2] image px (cuda); target_weight: V x [K, J, 1]; meta: V dicts -- what
+        the training loop hands to criterion_dict['fundamental'].  confidence: None or V x [K, J] (or
+        [K, J, 1]) weights of each view's DLT rows, differentiable.  detach_point: the triangulated point is
+        a constant and only the direct term reaches the predictions."""
+        assert isinstance(joints_2d_list[0], torch.Tensor)
+        ops.require_cuda(*joints_2d_list)
+        batch_size = joints_2d_list[0].shape[0]
+        subject = meta[0]['subject']
+        subject = subject.cpu().numpy() if isinstance(subject, torch.Tensor) else np.asarray(subject)
+        assert batch_size == len(subject)
+        assert len(joints_2d_list) == self.nviews
+        idx = self.subject_indices(subject)
+        x = torch.stack(joints_2d_list, dim=0)                    # view-major [V, K, J, 2], as the kernels read it
+        w = None
+        if self.use_target_weight and target_weight is not None:
+            w = torch.stack([t.reshape(batch_size, -1) for t in target_weight], dim=1)
+        c = None
+        if confidence is not None:
+            c = torch.stack([t.reshape(batch_size, -1) for t in confidence], dim=1)
+        return ops.reprojection_loss(self.M.index_select(0, idx), self.intr.index_select(0, idx), x, None, c, w,
+                                     undistort=not self.no_distortion, view_major=True,
+                                     detach_point=detach_point)
 
 
 def _not_built(name, why):

@@ -152,6 +152,12 @@ _SIGNATURES = {
     'posu_fundamental_workspace': [_i, _i, _i],
     'posu_fundamental_lmeds': [_p, _p, _i, _i, _i, _ull, _i, _p, _p, _p, _p, _p, _ll, _p],
     'posu_epipolar_residual_stats': [_p, _p, _p, _i, _i, _p, _p],
+    # differentiable triangulation and the reprojection loss (additive to ABI 16)
+    'posu_triangulate_dlt_w': [_p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p],
+    'posu_triangulate_dlt_bwd': [_p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p],
+    'posu_reprojection_loss_workspace': [_i, _i],
+    'posu_reprojection_loss_fwd': [_p, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _ll, _p],
+    'posu_reprojection_loss_bwd': [_p, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p],
 }
 _RESTYPES = {'posu_last_error': ctypes.c_char_p, 'posu_conv2d_wgrad_workspace': ctypes.c_longlong,
              'posu_pack_job_blocks': ctypes.c_longlong,
@@ -161,7 +167,8 @@ _RESTYPES = {'posu_last_error': ctypes.c_char_p, 'posu_conv2d_wgrad_workspace': 
              'posu_heatmap_dparams_floats': ctypes.c_longlong, 'posu_pair_mi_workspace': ctypes.c_longlong,
              'posu_pck_accuracy_workspace': ctypes.c_longlong, 'posu_grad_row_norms_workspace': ctypes.c_longlong,
              'posu_pseudo_label_workspace': ctypes.c_longlong, 'posu_sample_workspace': ctypes.c_longlong,
-             'posu_decode_views_workspace': ctypes.c_longlong, 'posu_fundamental_workspace': ctypes.c_longlong}
+             'posu_decode_views_workspace': ctypes.c_longlong, 'posu_fundamental_workspace': ctypes.c_longlong,
+             'posu_reprojection_loss_workspace': ctypes.c_longlong}
 
 
 def library_path():

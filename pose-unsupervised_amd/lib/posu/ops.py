@@ -603,6 +603,131 @@ def reproject(M, intr, xy, vis=None, undistort=True):
     return proj, res
 
 
+# ------------------------------------- differentiable triangulation, reprojection loss
+def _tri_args(M, intr, xy, vis, weights, target_weight, view_major):
+    """The tensors of the differentiable entry points in the layouts include/posu.h asks for: xy keeps its
+    layout (f64 stays, everything else is read as f32), the [G, V, J] tables are group-major f64."""
+    require_cuda(M, intr, xy, vis, weights, target_weight)
+    if view_major:
+        v, g, j, _ = xy.shape
+        sg, sv = j * 2, g * j * 2
+    else:
+        g, v, j, _ = xy.shape
+        sg, sv = v * j * 2, j * 2
+    if not 2 <= v <= 4:
+        raise ValueError('the differentiable triangulation takes 2 to 4 views, got %d' % v)
+    M = M.detach().contiguous().double()
+    intr = intr.detach().contiguous().double()
+    if vis is not None:
+        vis = vis.reshape(g, v, j).ne(0).to(torch.uint8).contiguous()
+    if weights is not None:
+        weights = weights.reshape(g, v, j)
+    if target_weight is not None:
+        target_weight = target_weight.detach().reshape(g, v, j).contiguous().double()
+    return M, intr, vis, weights, target_weight, (g, v, j, sg, sv)
+
+
+def _xy_storage(xy):
+    xy = xy.detach().contiguous()
+    return (xy, F64) if xy.dtype == torch.float64 else (xy.float(), F32)
+
+
+class _TriangulatePoints(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xy, w, M, intr, vis, dims, undistort):
+        g, v, j, sg, sv = dims
+        xs, code = _xy_storage(xy)
+        ws = None if w is None else w.detach().contiguous().double()
+        X = torch.empty((g, j, 3), dtype=torch.float64, device=xy.device)
+        call('posu_triangulate_dlt_w', ptr(M), ptr(intr), ptr(xs), code, sg, sv, ptr(vis), ptr(ws), g, v, j,
+             undistort, ptr(X), stream_of(xy.device))
+        ctx.save_for_backward(xs, ws, M, intr, vis)
+        ctx.args = (code, dims, undistort, xy.dtype, None if w is None else w.dtype)
+        return X
+
+    @staticmethod
+    def backward(ctx, gX):
+        xs, ws, M, intr, vis = ctx.saved_tensors
+        code, (g, v, j, sg, sv), undistort, xy_dtype, w_dtype = ctx.args
+        gX = gX.contiguous().double()
+        gxy = torch.empty_like(xs)
+        gw = None if ws is None else torch.empty_like(ws)
+        call('posu_triangulate_dlt_bwd', ptr(M), ptr(intr), ptr(xs), code, sg, sv, ptr(vis), ptr(ws), g, v, j,
+             undistort, ptr(gX), ptr(gxy), ptr(gw), stream_of(xs.device))
+        return (gxy.to(xy_dtype), None if gw is None else gw.to(w_dtype), None, None, None, None, None)
+
+
+def triangulate_points(M, intr, xy, vis=None, weights=None, undistort=True, view_major=False):
+    """triangulate_dlt for 2 to 4 views with a gradient: differentiable in xy and in weights, the optional
+    [G, V, J] confidence that multiplies the two DLT rows of a view.  M [G, V, 3, 4], intr [G, V, 9],
+    xy [G, V, J, 2] (or [V, G, J, 2] with view_major) f32|f64, vis [G, V, J] -> X [G, J, 3] f64."""
+    M, intr, vis, weights, _, dims = _tri_args(M, intr, xy, vis, weights, None, view_major)
+    return _TriangulatePoints.apply(xy, weights, M, intr, vis, dims, int(bool(undistort)))
+
+
+class _ReprojectionLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xy, w, M, intr, vis, omega, dims, undistort, detach_point):
+        g, v, j, sg, sv = dims
+        if g == 0:
+            raise ValueError('reprojection_loss: empty batch (the mean over G V J residuals is undefined)')
+        dev = xy.device
+        xs, code = _xy_storage(xy)
+        ws = None if w is None else w.detach().contiguous().double()
+        loss = torch.empty((), dtype=torch.float64, device=dev)
+        X = torch.empty((g, j, 3), dtype=torch.float64, device=dev)
+        nbytes = nat.load().posu_reprojection_loss_workspace(g, j)
+        if nbytes < 0:
+            raise ValueError('reprojection_loss: bad shape G = %d, J = %d' % (g, j))
+        workspace = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+        call('posu_reprojection_loss_fwd', ptr(M), ptr(intr), ptr(xs), code, sg, sv, ptr(vis), ptr(ws), ptr(omega),
+             g, v, j, undistort, ptr(loss), ptr(X), None, ptr(workspace), nbytes, stream_of(dev))
+        ctx.save_for_backward(xs, ws, M, intr, vis, omega)
+        ctx.args = (code, dims, undistort, detach_point, xy.dtype, None if w is None else w.dtype)
+        ctx.mark_non_differentiable(X)
+        return loss, X
+
+    @staticmethod
+    def backward(ctx, gloss, _gX):
+        xs, ws, M, intr, vis, omega = ctx.saved_tensors
+        code, (g, v, j, sg, sv), undistort, detach_point, xy_dtype, w_dtype = ctx.args
+        gloss = gloss.contiguous().double().reshape(1)
+        gxy = torch.empty_like(xs)
+        gw = None if ws is None else torch.empty_like(ws)
+        call('posu_reprojection_loss_bwd', ptr(M), ptr(intr), ptr(xs), code, sg, sv, ptr(vis), ptr(ws), ptr(omega),
+             g, v, j, undistort, detach_point, ptr(gloss), ptr(gxy), ptr(gw), stream_of(xs.device))
+        return (gxy.to(xy_dtype), None if gw is None else gw.to(w_dtype)) + (None,) * 7
+
+
+def reprojection_loss(M, intr, xy, vis=None, weights=None, target_weight=None, undistort=True, view_major=False,
+                      detach_point=False, return_points=False):
+    """The n-view reprojection-consistency loss (2 to 4 views): triangulate the predictions of all views (row
+    weights `weights`, as triangulate_points), project the point into every view with the lens model and average
+    the pixel distance to the predictions, weighted by `target_weight` [G, V, J]: sum / (G V J), an f64 scalar.
+    Differentiable in xy and weights; with detach_point the point is a constant (the online pseudo-label reading)
+    and only the direct term reaches xy.  return_points: -> (loss, X [G, J, 3] f64, no gradient)."""
+    M, intr, vis, weights, omega, dims = _tri_args(M, intr, xy, vis, weights, target_weight, view_major)
+    loss, X = _ReprojectionLoss.apply(xy, weights, M, intr, vis, omega, dims, int(bool(undistort)),
+                                      int(bool(detach_point)))
+    return (loss, X) if return_points else loss
+
+
+def reprojection_residuals(M, intr, xy, vis=None, weights=None, undistort=True, view_major=False):
+    """The loss's per-view pixel distances e [G, V, J] f64 and its points X [G, J, 3] f64 (no autograd)."""
+    M, intr, vis, weights, _, (g, v, j, sg, sv) = _tri_args(M, intr, xy, vis, weights, None, view_major)
+    dev = xy.device
+    xs, code = _xy_storage(xy)
+    ws = None if weights is None else weights.detach().contiguous().double()
+    loss = torch.empty((), dtype=torch.float64, device=dev)
+    X = torch.empty((g, j, 3), dtype=torch.float64, device=dev)
+    e = torch.empty((g, v, j), dtype=torch.float64, device=dev)
+    nbytes = nat.load().posu_reprojection_loss_workspace(g, j)
+    workspace = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=dev)
+    call('posu_reprojection_loss_fwd', ptr(M), ptr(intr), ptr(xs), code, sg, sv, ptr(vis), ptr(ws), None, g, v, j,
+         int(bool(undistort)), ptr(loss), ptr(X), ptr(e), ptr(workspace), nbytes, stream_of(dev))
+    return e, X
+
+
 # ----------------------------------------------------------------------- RPSM
 RPSM_MAX_BINS = 4096
 
